@@ -7,13 +7,17 @@ A "step" is one full MSM over the job's points, inputs already resident in HBM:
   N > 1: one MSM of N * 2^20 points, point-sharded (rank r holds points [r*2^20, (r+1)*2^20)),
          per-rank Pippenger on its GPU + ONE RCCL all-gather of the 96-byte Jacobian partials +
          rank-order fold on every rank (weak scaling: per-GPU work fixed).
-`value` = total points / (max-over-ranks time of K steps).  Secondary: the KZG decider over 256
-accumulators per GPU (config 3), pairings/s = 2 * accumulators / time.
-CPU baseline (rank 0, N = 1): the C++ restatement of util::msm::multi_scalar_multiplication
+`value` = total points / (max-over-ranks time of K steps).  Secondary (--full): the KZG decider over
+256 accumulators per GPU (config 3), pairings/s = 2 * accumulators / time.
+CPU baseline (--full; rank 0, N = 1): the C++ restatement of util::msm::multi_scalar_multiplication
 (oracle/, "kind": "port") on the SAME 2^20 input with the host's threads, plus the sequential
 decide_all on a 32-accumulator sample; the GPU result is checked against it (parity field).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]   (torchrun for N > 1)
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (torchrun for N > 1)
+A plain run sets up, warms up, times the K steps and prints the headline line (with the k_accumulate
+roofline, which comes from the timed steps' own HIP events).  --full adds everything that takes runs
+of its own: the sort / reduce breakdown, the host-buffer entry points, the decider, config 4, the
+batch-MSM / config-5 / Poseidon rows and the CPU baseline with its parity checks.
 """
 from __future__ import annotations
 
@@ -72,7 +76,27 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the batch-MSM / config-5 / Poseidon lines")
     ap.add_argument("--config4-log-n", type=int, default=24, help="one 2^k MSM split over the ranks (0: skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the stage breakdown, the host-buffer entry points, the KZG decider, "
+                         "config 4, the batch-MSM / config-5 / Poseidon lines and the CPU baseline with its parity "
+                         "checks (the --no-* and --config4-log-n options select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(path, result):
+    """The last timed step's return value -- the MSM's affine point, canonical integers (None: the
+    identity) -- as msm_point.npy: float64 (2, 16), row 0 = x and row 1 = y in 16-bit limbs, least
+    significant first (each limb exact in a float); the identity is all zeros, which is not on the
+    curve.  The inputs are seeded, so equal arguments give equal files."""
+    x, y = result if result is not None else (0, 0)
+    limbs = np.array([[(v >> (16 * k)) & 0xFFFF for k in range(16)] for v in (x, y)], dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "msm_point.npy"), limbs)
 
 
 def ref_window(n: int) -> int:
@@ -376,7 +400,7 @@ def main():
     torch.cuda.synchronize()
     acc_ms, span_ms = [], []
     # timed steps record only the accumulate's two HIP events (the live roofline); the sort /
-    # reduce split costs two more event records per call and is taken from one step afterwards
+    # reduce split costs two more event records per call and is taken from one step afterwards (--full)
     os.environ["SVGPU_MSM_LEAN"] = "1"
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -388,9 +412,12 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     os.environ["SVGPU_MSM_LEAN"] = "0"
-    step()
-    torch.cuda.synchronize()
-    stats = dv.last_msm_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
+    if args.full:  # one more step, with the sort / reduce split (breakdown_ms)
+        step()
+        torch.cuda.synchronize()
+    stats = dv.last_msm_stats()  # plain run: the last timed step's
     t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -403,7 +430,7 @@ def main():
     #      Rust; the H2D transfer is inside the timing) and sv_bn254_g1_msm_refs over shuffled
     #      references (NativeLoader's &[(&Fr, &G1Affine)] shape: the gather is inside too)
     host_api = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         hB = B.cpu().numpy().view(np.uint64).copy()
         hS = S.cpu().numpy().view(np.uint64).copy()
 
@@ -440,42 +467,43 @@ def main():
     # ---- KZG decider (config 3): accumulators per GPU (N > 1: rank r holds global accumulators
     #      [r dn, (r + 1) dn) and the first failing global index comes from one MIN all-reduce)
     dn = args.decider_n
-    # dn distinct valid accumulators per rank (rank r: the seeded t_i for i in [r dn, (r + 1) dn))
-    g2, sg2, accs = ob.gen_decider_case(dn, seed=ob.SEED_TRAPDOOR, start=rank * dn)
-    from svgpu import encoding as enc
-    L = torch.from_numpy(enc.bases_array([a[0] for a in accs]).view(np.int64)).to(dev)
-    R = torch.from_numpy(enc.bases_array([a[1] for a in accs]).view(np.int64)).to(dev)
+    if args.full:
+        # dn distinct valid accumulators per rank (rank r: the seeded t_i for i in [r dn, (r + 1) dn))
+        g2, sg2, accs = ob.gen_decider_case(dn, seed=ob.SEED_TRAPDOOR, start=rank * dn)
+        from svgpu import encoding as enc
+        L = torch.from_numpy(enc.bases_array([a[0] for a in accs]).view(np.int64)).to(dev)
+        R = torch.from_numpy(enc.bases_array([a[1] for a in accs]).view(np.int64)).to(dev)
 
-    def decide_step():
+        def decide_step():
+            if world > 1:
+                return parallel.sharded_decide_device(g2, sg2, L, R, rank * dn, svgpu.SV_CANONICAL)
+            ff_, _, _ = dv.decide(g2, sg2, L, R)
+            return ff_
+        # the decider line's own loop: a call is ~0.5 ms, so a few warm calls and at least 20 timed ones
+        # (5 right after one call read 0.56 ms per call on a box whose steady state was 0.52)
+        dwarm = max(3, args.warmup)
+        for _ in range(dwarm):
+            ff = decide_step()
+        dsteps = max(20, 2 * args.steps)
+        barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dec_kernel_ms = []
+        for _ in range(dsteps):
+            ff = decide_step()
+            dec_kernel_ms.append(dv.last_decide_kernel_ms())
+        torch.cuda.synchronize()
+        barrier()
+        dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=red_dev)
         if world > 1:
-            return parallel.sharded_decide_device(g2, sg2, L, R, rank * dn, svgpu.SV_CANONICAL)
-        ff_, _, _ = dv.decide(g2, sg2, L, R)
-        return ff_
-    # the decider line's own loop: a call is ~0.5 ms, so a few warm calls and at least 20 timed ones
-    # (5 right after one call read 0.56 ms per call on a box whose steady state was 0.52)
-    dwarm = max(3, args.warmup)
-    for _ in range(dwarm):
-        ff = decide_step()
-    dsteps = max(20, 2 * args.steps)
-    barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    dec_kernel_ms = []
-    for _ in range(dsteps):
-        ff = decide_step()
-        dec_kernel_ms.append(dv.last_decide_kernel_ms())
-    torch.cuda.synchronize()
-    barrier()
-    dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=red_dev)
-    if world > 1:
-        dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-    dec_s = float(dt.item())
-    pairings_per_s = 2 * dn * world * dsteps / dec_s
+            dist.all_reduce(dt, op=dist.ReduceOp.MAX)
+        dec_s = float(dt.item())
+        pairings_per_s = 2 * dn * world * dsteps / dec_s
 
     # ---- config 4: ONE 2^24-point MSM split over the N ranks (strong scaling; the north-star
     #      target is >= 1e8 scalar-muls/s at N = 8), inputs generated in each rank's HBM
     c4 = None
-    if args.config4_log_n > 0:
+    if args.full and args.config4_log_n > 0:
         del B, S
         torch.cuda.empty_cache()
         n4 = (1 << args.config4_log_n) // world
@@ -524,7 +552,7 @@ def main():
     # ---- "next" rows, rank 0 only: batched small MSMs, config-5 aggregation
     #      latency (accumulate 64 accumulators with r^i, then decide), batched Poseidon permutations
     extra = {}
-    if rank == 0 and not args.no_extras:
+    if args.full and rank == 0 and not args.no_extras:
         extra = next_rows(dev, dv, ob, enc, g2, sg2, accs)
 
     # ---- roofline of the dominant kernel (k_accumulate), timed with HIP events on its stream
@@ -572,6 +600,29 @@ def main():
     c_ref = ref_window(n)
     W_ref = -(-256 // c_ref)
     ref_macs = (W_ref * n * 11 + W_ref * 2 * ((1 << c_ref) - 1) * 16) * MACS_PER_FPMUL
+    kzg = None
+    if args.full:
+        kzg = {
+            "pairings_per_s": pairings_per_s,
+            "checks_per_s": pairings_per_s / 2,
+            "accumulators_per_gpu": dn,
+            "ms_per_decide_all": dec_s / dsteps * 1e3,
+            "calls": {"warmup": dwarm, "timed": dsteps},
+            "kernel_ms": float(np.mean(dec_kernel_ms)),
+            "first_fail": ff,
+            "fpmul_per_check": {"h2c_restatement_counted": FPMUL_H2C_COUNTED,
+                                "plain_restatement_counted": FPMUL_RESTATEMENT},
+            "int_mac": {
+                "achieved": dn * FPMUL_H2C_COUNTED * MACS_PER_FPMUL / (np.mean(dec_kernel_ms) * 1e-3),
+                "frac": dn * FPMUL_H2C_COUNTED * MACS_PER_FPMUL / (np.mean(dec_kernel_ms) * 1e-3) / MAC_PEAK,
+                "frac_without_line_prep": dn * (FPMUL_H2C_COUNTED - FPMUL_H2C_LINE_PREP) * MACS_PER_FPMUL
+                                          / (np.mean(dec_kernel_ms) * 1e-3) / MAC_PEAK,
+                "peak": MAC_PEAK,
+                "unit": "MAC/s (v_mad_u64_u32), work = accumulators x h2c_restatement_counted Fq products x 136; "
+                        "frac_without_line_prep drops the %d products of the two G2 line preparations the kernel "
+                        "caches per key" % FPMUL_H2C_LINE_PREP,
+            },
+        }
 
     out = {
         "metric": "BN254 G1 MSM points/sec at 2^20 + KZG pairings/sec; 1/2/4/8 GPU",
@@ -602,30 +653,10 @@ def main():
                                   "decider: MIN all-reduce of first_fail"}
                      if world > 1 else {"backend": None, "world_size": 1}),
         },
-        "kzg": {
-            "pairings_per_s": pairings_per_s,
-            "checks_per_s": pairings_per_s / 2,
-            "accumulators_per_gpu": dn,
-            "ms_per_decide_all": dec_s / dsteps * 1e3,
-            "calls": {"warmup": dwarm, "timed": dsteps},
-            "kernel_ms": float(np.mean(dec_kernel_ms)),
-            "first_fail": ff,
-            "fpmul_per_check": {"h2c_restatement_counted": FPMUL_H2C_COUNTED,
-                                "plain_restatement_counted": FPMUL_RESTATEMENT},
-            "int_mac": {
-                "achieved": dn * FPMUL_H2C_COUNTED * MACS_PER_FPMUL / (np.mean(dec_kernel_ms) * 1e-3),
-                "frac": dn * FPMUL_H2C_COUNTED * MACS_PER_FPMUL / (np.mean(dec_kernel_ms) * 1e-3) / MAC_PEAK,
-                "frac_without_line_prep": dn * (FPMUL_H2C_COUNTED - FPMUL_H2C_LINE_PREP) * MACS_PER_FPMUL
-                                          / (np.mean(dec_kernel_ms) * 1e-3) / MAC_PEAK,
-                "peak": MAC_PEAK,
-                "unit": "MAC/s (v_mad_u64_u32), work = accumulators x h2c_restatement_counted Fq products x 136; "
-                        "frac_without_line_prep drops the %d products of the two G2 line preparations the kernel "
-                        "caches per key" % FPMUL_H2C_LINE_PREP,
-            },
-        },
+        "kzg": kzg,
         "breakdown_ms": {k: round(stats[k], 4) for k in
                          ("sort_ms", "accumulate_ms", "reduce_ms", "host_ms", "total_ms")},
-        "breakdown_note": "HIP events on the library stream: sort_ms = digit extraction + two-level counting sort "
+        "breakdown_note":"HIP events on the library stream: sort_ms = digit extraction + two-level counting sort "
                           "(digits never stored; the GLV halves kept for the scatter pass), reduce_ms = bucket fixup + reduction, host_ms = host Horner; "
                           "finer splits with SVGPU_MSM_STATS=1 (each extra event costs ~5 us of GPU idle)",
         "roofline": {
@@ -662,12 +693,15 @@ def main():
         },
     }
 
+    if not args.full:  # the decider line and the sort / reduce split take runs of their own
+        for k in ("kzg", "breakdown_ms", "breakdown_note"):
+            del out[k]
     if host_api is not None:
         out["host_api"] = host_api
     if c4 is not None:
         out["config4_msm_2_24"] = c4
     out.update(extra)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, n, result, g2, sg2, accs, enc)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -30,6 +30,33 @@ def q2(v):
     return None if v is None else ((int(v[0][0], 16), int(v[0][1], 16)), (int(v[1][0], 16), int(v[1][1], 16)))
 
 
+_SANITIZER_PREFIX = None
+
+
+def sanitizer_prefix():
+    """Command prefix for a host binary built with a sanitizer.  The sanitizer runtimes reserve fixed
+    address ranges; where the kernel randomises mappings over more bits than the runtime allows for
+    (vm.mmap_rnd_bits = 32 against gcc 11's runtimes), a start lands in a reserved range now and
+    then and the process dies before main ("unexpected memory mapping").  `setarch -R` turns the
+    randomisation off for that one process; where setarch is missing or may not do so, the prefix
+    is empty and the binary runs as it is."""
+    global _SANITIZER_PREFIX
+    if _SANITIZER_PREFIX is None:
+        import platform
+        import shutil
+        import subprocess
+        _SANITIZER_PREFIX = []
+        setarch = shutil.which("setarch")
+        if setarch:
+            pre = [setarch, platform.machine(), "-R"]
+            try:
+                if subprocess.run(pre + ["true"], capture_output=True, timeout=30).returncode == 0:
+                    _SANITIZER_PREFIX = pre
+            except (OSError, subprocess.TimeoutExpired):
+                pass
+    return list(_SANITIZER_PREFIX)
+
+
 @pytest.fixture(scope="session")
 def golden_msm():
     return load_golden("msm.json")

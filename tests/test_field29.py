@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+from conftest import sanitizer_prefix
 from oracle import bn254 as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,6 +26,10 @@ def f29(request):
     return os.path.join(NATIVE, "build", request.param)
 
 
+def _cmd(binary, *args):
+    return (sanitizer_prefix() if binary.endswith("_asan") else []) + [binary, *args]
+
+
 def _limbs(h):
     """The harness prints a value as its 9 limbs, most significant first, 8 hex digits each."""
     if len(h) != 72:
@@ -37,7 +42,7 @@ def test_field_ops_values_and_bounds(f29, field):
     """Every operation over both moduli (FqM29 = p for the bucket chain, FrM29 = r for Poseidon)."""
     P = ob.P if field == "fq" else ob.R  # noqa: N806 (the modulus of this run)
     RINV = pow((1 << 261) % P, -1, P)  # noqa: N806
-    args = [f29] if field == "fq" else [f29, "fr"]
+    args = _cmd(f29) if field == "fq" else _cmd(f29, "fr")
     out = subprocess.run(args, capture_output=True, text=True, check=True).stdout
     counts = {}
     for line in out.splitlines():
@@ -160,7 +165,7 @@ def test_madd_group_law(f29, neg, live):
         cases.append((st, xb, yb, want))
     inp = "\n".join(" ".join(hex(v) for v in (*st, xb, yb)) for st, xb, yb, _ in cases) + "\n"
     mode = ("maddl" if live else "madd") + ("n" if neg else "")  # live: start / madd_live (round 6)
-    out = subprocess.run([f29, mode], input=inp, capture_output=True, text=True,
+    out = subprocess.run(_cmd(f29, mode), input=inp, capture_output=True, text=True,
                          check=True).stdout.splitlines()
     assert len(out) == len(cases)
     for (st, xb, yb, want), line in zip(cases, out):
@@ -196,7 +201,7 @@ def test_xyzz_add_group_law(f29):
         want = pb if pa is None else (pa if pb is None else ob.g1_add(pa, pb))
         cases.append((sa, sb, want))
     inp = "\n".join(" ".join(hex(v) for v in (*sa, *sb)) for sa, sb, _ in cases) + "\n"
-    out = subprocess.run([f29, "xadd"], input=inp, capture_output=True, text=True, check=True).stdout.splitlines()
+    out = subprocess.run(_cmd(f29, "xadd"), input=inp, capture_output=True, text=True, check=True).stdout.splitlines()
     assert len(out) == len(cases)
     for (sa, sb, want), line in zip(cases, out):
         X, Y, ZZ, ZZZ = (_limbs(v) for v in line.split())

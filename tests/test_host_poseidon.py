@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+from conftest import sanitizer_prefix
 from oracle import poseidon as op
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +25,8 @@ def sponge_bin(request):
 
 def _run(binary, state, elements):
     inp = ("-" if state is None else " ".join(hex(v) for v in state)) + "\n" + "\n".join(hex(e) for e in elements)
-    out = subprocess.run([binary], input=inp, capture_output=True, text=True, check=True).stdout.split()
+    cmd = (sanitizer_prefix() if binary.endswith("_asan") else []) + [binary]
+    out = subprocess.run(cmd, input=inp, capture_output=True, text=True, check=True).stdout.split()
     return int(out[0], 16), [int(v, 16) for v in out[1:4]]
 
 
