@@ -1,11 +1,14 @@
 // XYZZ mixed addition over field29.hpp's 9 x 29-bit limbs (round 4): k_accumulate's inner step.
 //
 // Bounds (field29.hpp's lazy contract), kept by every function here:
-//   state  X < 4p, Y < 2p, ZZ < 2p, ZZZ < 2p; the identity is exactly all-zero limbs (ZZ == 0: a
-//          non-identity state never has ZZ = 0 mod p, since ZZ3 = ZZ PP and PP != 0 mod p);
-//          madd's chain state (round 5) lets X reach 8p: its X3 skips the conditional subtraction,
-//          and whoever stores the chain's sum brings X below 4p (k_accumulate: csub<4> at a
-//          segment's end, AccChain<true>::out);
+//   state  Y < 2p, ZZ < 2p, ZZZ < 2p.  X < 8p raw for the chain (madd, madd_live, dbl_start: X3
+//          skips the conditional subtraction; k_accumulate stores the chain's state as it is, and
+//          the record's readers bring X below 4p with csub<4> before to_r32), X < 4p out of add.
+//          add and add_x8 take X < 8p on both sides: k_accumulate hands them chain states
+//          (tests/f29_cases.py runs them with X up to 8p - 1).
+//          The identity is ZZ == 0 ONLY; its other limbs are arbitrary (a cancelled chain zeroes ZZ
+//          and leaves X, Y, ZZZ as they were), so every reader tests ZZ alone.  A non-identity
+//          state never has ZZ = 0 mod p, since ZZ3 = ZZ PP and PP != 0 mod p;
 //   point  x2, y2 below 2p (R' form), never the identity (callers skip it).
 // The formulas are madd-2008-s / mdbl-2008-s, as xyzz_madd_2p / xyzz_mdbl in curve.hpp.
 #pragma once
@@ -63,10 +66,10 @@ SV29_HD Xyzz madd(const Xyzz& p, const F& x2, const F& y2, bool neg) {
 SV29_HD Xyzz madd(const Xyzz& p, const F& x2, const F& y2) { return madd(p, x2, y2, false); }
 
 // Round 6: the bucket chain's two halves of madd for a loop that never lets its state be the
-// identity (k_accumulate, SVGPU_ACC_LOOP=1): a segment starts with its first point (start) in the
+// identity (k_accumulate): a segment starts with its first point (start) in the
 // loop's divergent segment-end block, and the per-entry step (madd_live) has no identity test and
 // no identity-valued exit -- the merges those needed cost ~100 VALU instructions per entry (register
-// copies, 36 zeroing moves, the identity branch).  P + (-P) sets `cancel` and leaves a meaningless
+// copies, 36 zeroing moves, the identity branch).  P + (-P) sets `special` to 1 and leaves a meaningless
 // state: the caller marks the chain empty and restarts it with its next point.
 // (x2, -y2) starts as (x2, y2, 1, -1): y = Y / ZZZ, and ZZ^3 = ZZZ^2 still holds (Z = -1), so the sign
 // is a choice between two constants for ZZZ instead of a subtraction pass over y2
@@ -107,13 +110,25 @@ SV29_HD Xyzz dbl_start(const F& x2, const F& y2, bool neg) {
   return {X3, Y3, PP, PPP};
 }
 
-// p + q, both XYZZ states (bounds as above; either may be the identity).  add-2008-s; the
+// p + q, both XYZZ states (X < 8p in; either may be the identity).  add-2008-s; the
 // doubling case (p = q) runs through the same products as in madd: dbl-2008-s-1's U = 2Y, M = 3X²,
 // S = X V, ZZ3 = V ZZ, ZZZ3 = W ZZZ are the addition's Pd, Rd, Q, ZZ3, ZZZ3 with U1 = X, S1 = Y and
 // q's ZZ, ZZZ taken as 1, and no PPP term in X3.
-SV29_HD Xyzz add(const Xyzz& p, const Xyzz& q) {
-  if (is_identity(p)) return q;
-  if (is_identity(q)) return p;
+// An identity operand returns the other one, whose X may be a chain state's (below 8p, not 4p).
+// add (kX4) brings it below 4p, so that X < 4p holds out of every path; add_x8 returns it as it
+// came, X < 8p out, for a writer whose readers take that anyway: k_accumulate's in-block join
+// writes a bucket record, and the extra pass there cost the chain's kernel its registers
+// (k_accumulate<false, true>: 123 VGPRs and no spill without it, 128 and 3 spilled with it).
+template <bool kX4>
+SV29_HD Xyzz add_t(const Xyzz& p, const Xyzz& q) {
+  if (is_identity(p)) {
+    if constexpr (kX4) return {csub<4>(q.X), q.Y, q.ZZ, q.ZZZ};
+    else return q;
+  }
+  if (is_identity(q)) {
+    if constexpr (kX4) return {csub<4>(p.X), p.Y, p.ZZ, p.ZZZ};
+    else return p;
+  }
   F U1 = mul(p.X, q.ZZ), S1 = mul(p.Y, q.ZZZ);                  // < 2p
   F Pd = sub<2>(mul(q.X, p.ZZ), U1), Rd = sub<2>(mul(q.Y, p.ZZZ), S1);  // < 4p
   F qZZ = q.ZZ, qZZZ = q.ZZZ;
@@ -131,6 +146,8 @@ SV29_HD Xyzz add(const Xyzz& p, const Xyzz& q) {
   const F Y3 = mul_sum2(Rd, sub<4>(Q, X3), S1, sub<2>(zero(), PPP));
   return {X3, Y3, mul(mul(p.ZZ, qZZ), PP), mul(mul(p.ZZZ, qZZZ), PPP)};
 }
+SV29_HD Xyzz add(const Xyzz& p, const Xyzz& q) { return add_t<true>(p, q); }      // X < 4p out
+SV29_HD Xyzz add_x8(const Xyzz& p, const Xyzz& q) { return add_t<false>(p, q); }  // X < 8p out
 
 }  // namespace r29
 }  // namespace sv

@@ -416,8 +416,9 @@ SV29_HD bool is_zero(const F29<M>& a) {
 
 // a == 0 mod p for a below 16p (Fq only): a in {0, p, .., 15p}.  Round 6: the one multiple k p a
 // can equal comes from its top limb, k = round(a_8 / (p / 2^232)) in float (the multiples' top
-// limbs are ~3.17e6 apart, so the rounding is exact for every k < 16; tests/test_field29.py checks
-// all sixteen), and limb 0 must match k p's; the full comparison runs only on that rare path.  The
+// limbs are ~3.17e6 apart, so the rounding is exact for every k < 16, fused into one multiply-add
+// as on the device or rounded twice as on the host; tests/f29_cases.py checks all sixteen and their
+// neighbours through both builds), and limb 0 must match k p's; the full comparison runs only on that rare path.  The
 // round-5 filter compared limb 0 with each multiple, which the compiler lowered to a binary search
 // of divergent branches: ~60 SALU instructions per bucket entry.
 SV29_HD bool is_zero_mod_p_16p(const F& a) {

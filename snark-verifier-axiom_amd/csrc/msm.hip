@@ -114,6 +114,9 @@ __device__ __forceinline__ void store_xyzz(G1Xyzz* __restrict__ a, uint32_t i, c
 // end is nine 16-B stores and no conversion (round 4-5 packed the limbs into 8-word x R' values
 // after a conditional subtraction of 4p: ~110 VALU instructions in the accumulate's divergent
 // segment-end block, i.e. ~70 per bucket entry at 2^20).  The readers convert once per bucket.
+// In a record the identity is ZZ == 0 only; its other limbs are arbitrary (a cancelled chain zeroes
+// ZZ and stores X, Y, ZZZ as they were), so st_rec29 / ld_rec29 move the limbs as they are and every
+// reader tests ZZ alone (r29::is_identity; tests/f29_cases.py's garbage-identity cases).
 // Arrays stay typed G1Xyzz*: rec_at gives record i of either form.
 constexpr uint32_t kRec29Words = 4 * r29::L;  // 36
 __host__ __device__ __forceinline__ size_t bucket_rec_bytes(int r29) { return r29 ? 4 * kRec29Words : sizeof(G1Xyzz); }
@@ -1158,8 +1161,8 @@ __global__ void __launch_bounds__(kBlock, R29 ? SV_ACC29_MIN_BLOCKS : SV_ACC_MIN
   }
   __syncthreads();
   if (owner) {
-    if constexpr (R29)  // the two pieces added in the chain's own form (r29::add takes X below 12p)
-      st_rec29(bsum, g, r29::add(acc, ld_rec29(reinterpret_cast<const G1Xyzz*>(shead29), threadIdx.x + 1)));
+    if constexpr (R29)  // the two pieces added in the chain's own form (X below 8p in, and out: a record's bound)
+      st_rec29(bsum, g, r29::add_x8(acc, ld_rec29(reinterpret_cast<const G1Xyzz*>(shead29), threadIdx.x + 1)));
     else
       store_xyzz(bsum, g, xyzz_add(sum, shead[threadIdx.x + 1]));
   }

@@ -1,6 +1,8 @@
 // Test harness (not part of libsvgpu): every operation of csrc/field29.hpp on the host, over random
 // and boundary operands at the bounds the header states; prints "op inputs... output" lines (hex
 // integers) for tests/test_field29.py, which checks values mod p and output bounds with Python ints.
+// "cases" mode: the cases of tests/f29_cases.py from stdin (operands up to the stated bounds), through
+// the dispatch shared with the device harness (f29_ops.hpp).
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -9,6 +11,7 @@
 #include <type_traits>
 
 #include "curve29.hpp"
+#include "f29_ops.hpp"
 
 using namespace sv::r29;
 
@@ -202,7 +205,37 @@ static int xadd_mode() {
   return 0;
 }
 
+// "cases" mode: stdin lines "op field flag limbs..." (op as f29_ops.hpp numbers it, field 0 = Fq,
+// 1 = Fr, then n_in(op) slots of 9 hex words) -> n_out(op) slots of 9 hex words and the flag, for
+// the cases of tests/f29_cases.py
+template <class M>
+static bool run_case(int op, const uint32_t* in, uint32_t* out, uint32_t& flag) {
+  switch (op) {
+#define CASE(OP) \
+  case f29t::OP: f29t::run<f29t::OP, M>(in, out, flag); return true;
+    F29T_FOR_EACH_OP(CASE)
+#undef CASE
+  }
+  return false;
+}
+static int cases_mode() {
+  int op, field;
+  uint32_t flag;
+  while (scanf("%d %d %x", &op, &field, &flag) == 3) {
+    if (op < 0 || op >= f29t::OP_COUNT || field < 0 || field > 1 || (field == 1 && f29t::fq_only(op))) return 2;
+    uint32_t in[f29t::MAX_IN * f29t::SLOT], out[f29t::MAX_OUT * f29t::SLOT] = {};
+    const int ni = f29t::n_in(op) * f29t::SLOT, no = f29t::n_out(op) * f29t::SLOT;
+    for (int i = 0; i < ni; i++)
+      if (scanf("%x", &in[i]) != 1) return 2;
+    if (!(field == 0 ? run_case<FqM29>(op, in, out, flag) : run_case<FrM29>(op, in, out, flag))) return 2;
+    for (int i = 0; i < no; i++) printf("%x ", out[i]);
+    printf("%x\n", flag);
+  }
+  return feof(stdin) ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "cases")) return cases_mode();
   if (argc > 1 && !strcmp(argv[1], "madd")) return madd_mode();
   if (argc > 1 && !strcmp(argv[1], "maddn")) return g_neg = true, madd_mode();
   if (argc > 1 && !strcmp(argv[1], "maddl")) return g_live = true, madd_mode();

@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+import f29_cases as fc
 from conftest import sanitizer_prefix
 from oracle import bn254 as ob
 
@@ -210,3 +211,44 @@ def test_xyzz_add_group_law(f29):
         assert got == (None if want is None else tuple(want)), (sa, sb)
         if got is None:
             assert X == Y == ZZ == ZZZ == 0, line
+
+
+# The shared cases of tests/f29_cases.py (operands at the stated bounds; nothing skipped), through the
+# harness's "cases" mode; tests/test_gpu_field29.py runs the same cases through the device build.
+def _run_cases(f29, jobs):
+    """jobs: (op id, field id, rows, flags).  One process; a result row and flag per case, per job."""
+    inp = "".join("%d %d %x %s\n" % (op, field, fl, " ".join("%x" % x for x in row))
+                  for op, field, rows, flags in jobs for row, fl in zip(rows, flags))
+    out = subprocess.run(_cmd(f29, "cases"), input=inp, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == sum(len(rows) for _, _, rows, _ in jobs)
+    res, at = [], 0
+    for _, _, rows, _ in jobs:
+        lines = [[int(x, 16) for x in line.split()] for line in out[at:at + len(rows)]]
+        res.append(([v[:-1] for v in lines], [v[-1] for v in lines]))
+        at += len(rows)
+    return res
+
+
+@pytest.mark.parametrize("field", ["fq", "fr"])
+def test_field_ops_at_stated_bounds(f29, field):
+    """Every field operation over operands up to its stated input bound (12p, 9p, 8p, 2 K p - 1, ...),
+    worst-limb values and all-at-the-bound tuples: value mod the modulus and output bound."""
+    names = [n for n, f in fc.FIELD_CASES if f == field]
+    jobs = [(fc.OPS[n].id, fc.FIELD_ID[field], *fc.field_rows(n, field)) for n in names]
+    checked = 0
+    for n, (rows, flags) in zip(names, _run_cases(f29, jobs)):
+        got = fc.check_field(n, field, rows, flags)
+        assert got >= 2000, n
+        checked += got
+    assert checked == sum(len(j[2]) for j in jobs)  # zero cases skipped
+
+
+def test_curve_ops_chosen_cases(f29):
+    """madd, the loop's start / madd_live / dbl_start, r29::add and add_x8 over chosen kinds: chain states
+    with X up to x + 7p, doubling across representations, cancellation, clean and garbage
+    identities (ZZ == 0 alone marks one)."""
+    jobs = [(fc.CURVE_IDS[n], 0, *fc.curve_rows(n, neg)) for n, neg in fc.CURVE_CASES]
+    checked = 0
+    for (n, neg), (rows, flags) in zip(fc.CURVE_CASES, _run_cases(f29, jobs)):
+        checked += fc.check_curve(n, neg, rows, flags)
+    assert checked == sum(len(j[2]) for j in jobs)
