@@ -182,6 +182,47 @@ int sv_bn254_g1_msm_batch_indexed_device(const sv_g1_affine* d_table, size_t tab
                                          int form, int device, void* stream,
                                          sv_g1_affine* d_out) SV_NOEXCEPT;
 
+/* ---- resident base sets for large MSMs ------------------------------------------------
+ * The bases of a KZG MSM are almost never new (the SRS, a Lagrange basis, a committing key): a
+ * base set uploads n affine points ONCE and keeps them on one device in the form the MSM
+ * pipeline consumes -- the Montgomery rows (64 B) and the accumulate's 29-bit table records of P
+ * and phi(P) (144 B), 208 B per point -- so that an MSM call ships only scalars (32 B per term
+ * instead of 96) and converts, checks or tabulates no base:
+ *   out = sum_{i<n} scalars[i] * set[offset + i];  `form` is the scalars' and the output's form.
+ * create / create_device (rows already in HBM on `device`, `stream` may be NULL): `device` is the
+ * index of an initialised device, as for sv_bn254_g1_table_create; coordinates must be reduced
+ * (checked on the device: SV_ERR_ARG, no handle is issued and nothing stays allocated); identity
+ * rows (0, 0) are legal and contribute nothing; n > 2^26 is SV_ERR_LEN.  The caller's rows are
+ * not retained.  info: rows, device index and bytes held on the device (any of the three may be
+ * NULL).  msm_bases takes host scalars (fed in pieces like sv_bn254_g1_msm -- default: pieces
+ * weighted 1,3,4 from 2^20 terms, 1,3 from 2^18, else one; SVGPU_H2D_PIECES / SVGPU_H2D_SPLIT
+ * apply -- a piece is accumulated as soon as its own sort is done: there is no base transfer to
+ * wait for), msm_bases_device scalars in HBM on the set's device and returns the
+ * Jacobian partial like sv_bn254_g1_msm_device.  Checked before any device work, in this order:
+ * bad form or null pointer SV_ERR_ARG, n == 0 SV_ERR_EMPTY, n > 2^26 SV_ERR_LEN, unknown or
+ * destroyed handle SV_ERR_ARG (a base-table handle is not a base-set handle, nor the reverse),
+ * offset + n beyond the set SV_ERR_ARG.  An unreduced scalar is SV_ERR_ARG for that call; the
+ * handle stays usable.  The plan (window size, GLV, ...) follows the call's n, not the set's
+ * size; calls of at most 256 terms take the small-MSM route over the set's rows.  Resident calls
+ * always run the 29-bit accumulate chain (SVGPU_ACC_R29 does not apply) and fill
+ * sv_msm_last_stats like the other MSM calls.
+ * Handles are process-wide and thread-safe: any number of threads may run MSMs on one handle at
+ * once (the set is read-only).  Destroying a handle while another thread is inside a call that
+ * uses it is a caller error, as it is for base tables.
+ * One handle lives on ONE device; there is no multi-device handle.  A caller with several GPUs
+ * makes one set per device over its shard of the bases, calls msm_bases_device per device and
+ * folds the Jacobian partials with sv_bn254_g1_fold.                                          */
+int sv_bn254_g1_bases_create(const sv_g1_affine* bases, size_t n, int form, int device,
+                             uint64_t* handle) SV_NOEXCEPT;
+int sv_bn254_g1_bases_create_device(const sv_g1_affine* d_bases, size_t n, int form, int device,
+                                    void* stream, uint64_t* handle) SV_NOEXCEPT;
+int sv_bn254_g1_bases_destroy(uint64_t handle) SV_NOEXCEPT;
+int sv_bn254_g1_bases_info(uint64_t handle, uint64_t* n, int* device, uint64_t* device_bytes) SV_NOEXCEPT;
+int sv_bn254_g1_msm_bases(uint64_t handle, size_t offset, const sv_fe* scalars, size_t n, int form,
+                          sv_g1_affine* out) SV_NOEXCEPT;
+int sv_bn254_g1_msm_bases_device(uint64_t handle, size_t offset, const sv_fe* d_scalars, size_t n,
+                                 int form, void* stream, sv_g1_jacobian* out_partial) SV_NOEXCEPT;
+
 /* ---- Poseidon sponge over BN254 Fr --------------------------
  * x^5 HADES permutation, width t = 3 (R_F 8, R_P 57, rate 2: the SDK's PoseidonTranscript,
  * snark-verifier-sdk/src/halo2.rs:52-71) or t = 5 (R_F 8, R_P 60, rate 4).  States are t

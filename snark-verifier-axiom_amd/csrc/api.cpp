@@ -883,6 +883,206 @@ int sv_bn254_g1_msm_batch_indexed_device(const sv_g1_affine* d_table, size_t tab
   SV_GUARD_END
 }
 
+// ---- resident base sets (upload once, ship only scalars per MSM call) -----------------------
+namespace {
+struct BaseSet {
+  int index = 0;         // the logical device the caller asked for
+  int dev = 0;           // its HIP ordinal
+  void* rows = nullptr;  // n Montgomery rows
+  void* vtab = nullptr;  // 2 n records of the 29-bit table (msm.hpp)
+  size_t n = 0;
+};
+// handles come from the base tables' counter, so no number is ever both a table and a set
+std::unordered_map<uint64_t, BaseSet> g_sets;
+
+constexpr size_t kMaxSetRows = size_t(1) << 26;
+
+bool set_lookup(uint64_t h, BaseSet* out) {
+  std::lock_guard<std::mutex> lk(g_tables_mu);
+  auto it = g_sets.find(h);
+  if (it == g_sets.end()) {
+    sv::set_error("unknown base set handle %llu", (unsigned long long)h);
+    return false;
+  }
+  *out = it->second;
+  return true;
+}
+
+// checks shared by the two create variants; nothing touches a device before they pass
+int set_create_args(const void* bases, size_t n, int form, const uint64_t* handle) {
+  SV_TRY(check_form(form));
+  if (!handle || !bases) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (n == 0) {
+    sv::set_error("empty base set");
+    return SV_ERR_EMPTY;
+  }
+  if (n > kMaxSetRows) {
+    sv::set_error("n = %zu exceeds the per-device limit 2^26 (one set per device over its shard)", n);
+    return SV_ERR_LEN;
+  }
+  return SV_OK;
+}
+
+// rows: host rows (from_device = false, uploaded) or rows in HBM on the set's device
+int set_create(const sv_g1_affine* rows, bool from_device, size_t n, int form, int device, hipStream_t stream,
+               uint64_t* handle) {
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  if (device < 0 || device >= runtime_device_count()) {
+    sv::set_error("device %d not initialised", device);
+    return SV_ERR_ARG;
+  }
+  BaseSet t;
+  t.index = device;
+  t.dev = runtime_device_id(device);
+  t.n = n;
+  SV_HIP(hipSetDevice(t.dev));
+  if (hipMalloc(&t.rows, n * kResidentRowBytes) != hipSuccess ||
+      hipMalloc(&t.vtab, n * kResidentTabBytes) != hipSuccess) {
+    (void)hipGetLastError();
+    if (t.rows) (void)hipFree(t.rows);
+    sv::set_error("base set: hipMalloc of %zu rows failed", n);
+    return SV_ERR_OOM;
+  }
+  int rc = SV_OK;
+  if (!from_device && hipMemcpy(t.rows, rows, n * sizeof(sv_g1_affine), hipMemcpyHostToDevice) != hipSuccess) {
+    sv::set_error("base set upload failed");
+    rc = SV_ERR_DEVICE;
+  }
+  if (rc == SV_OK) rc = msm_resident_prepare(from_device ? (const void*)rows : t.rows, n, form, t.dev, stream, t.rows, t.vtab);
+  if (rc != SV_OK) {  // no handle, nothing kept
+    (void)hipFree(t.rows);
+    (void)hipFree(t.vtab);
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(g_tables_mu);
+  *handle = g_next_table++;
+  g_sets[*handle] = t;
+  return SV_OK;
+}
+
+// the MSM calls' checks, in order: form / null, empty, length, handle, range (no device touched)
+int set_call_args(uint64_t handle, size_t offset, const void* scalars, size_t n, int form, const void* out,
+                  BaseSet* t) {
+  SV_TRY(check_form(form));
+  if (!scalars || !out) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (n == 0) {
+    sv::set_error("pairs should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (n > kMaxSetRows) {
+    sv::set_error("n = %zu exceeds the per-device limit 2^26 (shard across devices/calls)", n);
+    return SV_ERR_LEN;
+  }
+  if (!set_lookup(handle, t)) return SV_ERR_ARG;
+  if (offset > t->n || n > t->n - offset) {  // offset + n > N without the sum
+    sv::set_error("rows [%zu, %zu + %zu) reach past base set %llu (%zu rows)", offset, offset, n,
+                  (unsigned long long)handle, t->n);
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+}  // namespace
+
+int sv_bn254_g1_bases_create(const sv_g1_affine* bases, size_t n, int form, int device, uint64_t* handle) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(set_create_args(bases, n, form, handle));
+  return set_create(bases, false, n, form, device, nullptr, handle);
+  SV_GUARD_END
+}
+
+int sv_bn254_g1_bases_create_device(const sv_g1_affine* d_bases, size_t n, int form, int device, void* stream,
+                                    uint64_t* handle) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(set_create_args(d_bases, n, form, handle));
+  return set_create(d_bases, true, n, form, device, (hipStream_t)stream, handle);
+  SV_GUARD_END
+}
+
+int sv_bn254_g1_bases_destroy(uint64_t handle) noexcept {
+  SV_GUARD_BEGIN
+  BaseSet t;
+  {
+    std::lock_guard<std::mutex> lk(g_tables_mu);
+    auto it = g_sets.find(handle);
+    if (it == g_sets.end()) {
+      sv::set_error("unknown base set handle %llu", (unsigned long long)handle);
+      return SV_ERR_ARG;
+    }
+    t = it->second;
+    g_sets.erase(it);
+  }
+  SV_HIP(hipSetDevice(t.dev));
+  SV_HIP(hipFree(t.rows));
+  SV_HIP(hipFree(t.vtab));
+  return SV_OK;
+  SV_GUARD_END
+}
+
+int sv_bn254_g1_bases_info(uint64_t handle, uint64_t* n, int* device, uint64_t* device_bytes) noexcept {
+  SV_GUARD_BEGIN
+  BaseSet t;
+  if (!set_lookup(handle, &t)) return SV_ERR_ARG;
+  if (n) *n = t.n;
+  if (device) *device = t.index;
+  if (device_bytes) *device_bytes = (uint64_t)t.n * (kResidentRowBytes + kResidentTabBytes);
+  return SV_OK;
+  SV_GUARD_END
+}
+
+int sv_bn254_g1_msm_bases(uint64_t handle, size_t offset, const sv_fe* scalars, size_t n, int form,
+                          sv_g1_affine* out) noexcept {
+  SV_GUARD_BEGIN
+  BaseSet t;
+  SV_TRY(set_call_args(handle, offset, scalars, n, form, out, &t));
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  MsmFeed feed;
+  feed.pieces = h2d_pieces();
+  // Piece schedule.  sv_bn254_g1_msm's (5,4,4,3 from 2^18, 2 equal from 2^15) was tuned for a 96-B
+  // copy that outlasts the accumulates; a 32-B copy does not, so what counts here is a small first
+  // piece (the accumulates start early) and few pieces (each accumulate is more efficient).  Swept
+  // with tools/resident_bench.py --sweep (profiles/resident_bases_ab.log, ms per call, three passes):
+  //   2^20: 1,3,4 1.91-1.93  1,2,5 1.92-1.93  1,3 1.98-2.02  2 equal 2.03-2.06  4 equal 2.02-2.06
+  //         5,4,4,3 2.12-2.15  1,7 2.14-2.17  1 piece 2.25-2.26
+  //   2^18: 1,3 1.39  1,7 1.39-1.40  2 equal 1.42  1,2,5 1.43  1 piece 1.47  5,4,4,3 1.60
+  //   2^16: 1 piece 0.74  1,2 0.78  1,7 0.78  1,3 0.82  2 equal 0.92  4 pieces 0.95
+  // so: one piece below 2^18 terms, 1,3 from there, 1,3,4 from 2^20 (the sizes between were not
+  // measured).  SVGPU_H2D_PIECES / SVGPU_H2D_SPLIT override it as for the other host entry points.
+  if (feed.pieces == 0 && n < (size_t(1) << 18)) feed.pieces = 1;
+  if (n >= (size_t(1) << 20)) feed.split = {1, 3, 4};
+  else feed.split = {1, 3};
+  feed.stage_scalars = [&](size_t a, size_t b, void* ds, hipStream_t cs, hipEvent_t ready) -> int {
+    SV_HIP(hipMemcpyAsync(ds, scalars + a, (b - a) * sizeof(sv_fe), hipMemcpyHostToDevice, cs));
+    SV_HIP(hipEventRecord(ready, cs));
+    return SV_OK;
+  };
+  const MsmResident set{t.rows, t.vtab, t.n, offset};
+  Xyzz r;
+  SV_TRY(msm_run_resident_fed(set, n, form, t.dev, feed, &r));
+  affine_out(r, form, out);
+  return SV_OK;
+  SV_GUARD_END
+}
+
+int sv_bn254_g1_msm_bases_device(uint64_t handle, size_t offset, const sv_fe* d_scalars, size_t n, int form,
+                                 void* stream, sv_g1_jacobian* out_partial) noexcept {
+  SV_GUARD_BEGIN
+  BaseSet t;
+  SV_TRY(set_call_args(handle, offset, d_scalars, n, form, out_partial, &t));
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  const MsmResident set{t.rows, t.vtab, t.n, offset};
+  Xyzz r;
+  SV_TRY(msm_run_resident_device(set, d_scalars, n, form, t.dev, (hipStream_t)stream, &r));
+  jacobian_out(r, out_partial);
+  return SV_OK;
+  SV_GUARD_END
+}
+
 int sv_bn254_poseidon_permute(sv_fe* states, size_t n, int t, int form) noexcept {
   SV_GUARD_BEGIN
   SV_TRY(check_form(form));

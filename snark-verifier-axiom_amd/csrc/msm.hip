@@ -417,6 +417,41 @@ __global__ void k_vtab(const G1Aff* __restrict__ bases, uint32_t n, uint4* __res
   if (i < n) vtab_put(bases, i, vtab, n, glv != 0, err);
 }
 
+// Resident base set (msm_resident_prepare), once per set: rows in either form -> Montgomery rows
+// (64 B per point, the small route's input) and the 29-bit table of the whole set, P_i at record i
+// and phi(P_i) at record n + i for every set size (any call size may take the GLV plan); unreduced
+// coordinates set the error flag.  in may equal out (a thread reads its row before it writes it), so
+// neither is __restrict__.  n <= 2^26: record n + i stays below 2^27.
+__global__ void __launch_bounds__(kBlock) k_resident_prepare(const G1Aff* in, G1Aff* out, uint32_t n, int mont_in,
+                                                             uint4* __restrict__ vtab, uint32_t* __restrict__ err) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  G1Aff a;
+  {
+    const uint4* p = reinterpret_cast<const uint4*>(in + i);
+    const uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+    a.x.v[0] = q0.x; a.x.v[1] = q0.y; a.x.v[2] = q0.z; a.x.v[3] = q0.w;
+    a.x.v[4] = q1.x; a.x.v[5] = q1.y; a.x.v[6] = q1.z; a.x.v[7] = q1.w;
+    a.y.v[0] = q2.x; a.y.v[1] = q2.y; a.y.v[2] = q2.z; a.y.v[3] = q2.w;
+    a.y.v[4] = q3.x; a.y.v[5] = q3.y; a.y.v[6] = q3.z; a.y.v[7] = q3.w;
+  }
+  if (!a.x.is_reduced() || !a.y.is_reduced()) {
+    atomicOr(err, 1u);
+    a.x = Fq::zero();  // the set is discarded: keep the stored limbs in range all the same
+    a.y = Fq::zero();
+  }
+  if (!mont_in && !a.is_identity()) {
+    a.x = fe_to_mont(a.x);
+    a.y = fe_to_mont(a.y);
+  }
+  uint4* o = reinterpret_cast<uint4*>(out + i);
+  o[0] = make_uint4(a.x.v[0], a.x.v[1], a.x.v[2], a.x.v[3]);
+  o[1] = make_uint4(a.x.v[4], a.x.v[5], a.x.v[6], a.x.v[7]);
+  o[2] = make_uint4(a.y.v[0], a.y.v[1], a.y.v[2], a.y.v[3]);
+  o[3] = make_uint4(a.y.v[4], a.y.v[5], a.y.v[6], a.y.v[7]);
+  vtab_put_pt(a, i, vtab, n, true, nullptr);
+}
+
 // Montgomery-form bases that no other pass reads before the accumulate (no GLV table, host-fed)
 __global__ void k_check_bases(const G1Aff* __restrict__ bases, uint32_t n, uint32_t* __restrict__ err) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -685,7 +720,9 @@ __global__ void __launch_bounds__(1024) k_bin_scan(const uint32_t* __restrict__ 
 
 // Pass 3: the block's entries are first placed in LDS grouped by (window, bin), then each group
 // is copied to its global run with consecutive lanes writing consecutive addresses.  Entry point
-// index: the virtual point (i, or n + i for a GLV k2 digit).  The block's own (window, bin) counts
+// index: the virtual point's table record, p_off + i, or phi_off + i for a GLV k2 digit (0 and n
+// for a table of this sort's own points; a resident base set's offset and phi stride otherwise).
+// The block's own (window, bin) counts
 // are not recounted: they are the differences of consecutive block offsets that k_bin_scan_chunks
 // left in bcnt (btot for the last block), which halves the LDS atomics of the pass.
 template <int C, bool GLV>
@@ -694,7 +731,8 @@ __global__ void __launch_bounds__(kBlock) k_bin_scatter(const Fr* __restrict__ s
                                                         const uint32_t* __restrict__ btot,
                                                         const uint32_t* __restrict__ bstart,
                                                         uint64_t* __restrict__ tmp, int e32, int xcd, int bm,
-                                                        uint32_t w0, uint32_t nw, const uint4* __restrict__ stored) {
+                                                        uint32_t w0, uint32_t nw, const uint4* __restrict__ stored,
+                                                        uint32_t p_off, uint32_t phi_off) {
   using D = Digits<C, GLV>;
   constexpr int W = D::W, LOGB = C - 1;
   constexpr int CB = coarse_bits(C, D::NB), FB = LOGB - CB, NBIN = 1 << CB, NK = W * NBIN;
@@ -751,7 +789,7 @@ __global__ void __launch_bounds__(kBlock) k_bin_scatter(const Fr* __restrict__ s
   __syncthreads();
   for (uint32_t x = threadIdx.x; x < total; x += kBlock) {
     const uint32_t e = stage[x];
-    const uint32_t pt = lo + (e & ((1u << LP) - 1u)) + (((e >> LP) & 1u) ? n : 0u);
+    const uint32_t pt = lo + (e & ((1u << LP) - 1u)) + (((e >> LP) & 1u) ? phi_off : p_off);
     const uint32_t dst = cur[e >> (LP + 2 + FB)] + x, fine = (e >> (LP + 2)) & FMASK, neg = (e >> (LP + 1)) & 1u;
     if (e32) reinterpret_cast<uint32_t*>(tmp)[dst] = pack_entry32(fine, neg, pt, FB);
     else tmp[dst] = ((uint64_t)fine << 32) | pt | (neg << 31);
@@ -1753,7 +1791,8 @@ MsmPlan msm_plan(size_t n) {
   p.tree = 1;
   if (const char* e = getenv("SVGPU_GROUP_TREE")) p.tree = atoi(e);
   // k_accumulate's chain (AccChain): the 29-bit one unless SVGPU_ACC_R29=0; fixed per call, so
-  // the accumulate, fixup and reduction launches of one MSM agree on the stored form
+  // the accumulate, fixup and reduction launches of one MSM agree on the stored form.  (A resident
+  // base set holds only the 29-bit table, so its calls use this chain whatever the switch says.)
   p.r29 = !getenv("SVGPU_ACC_R29") || atoi(getenv("SVGPU_ACC_R29")) != 0;
   if (p.tree == 2 && p.B % kTreeN == 0 && p.B / kTreeN <= 128) p.logL = 0;
   else if (p.tree == 2) p.tree = 1;
@@ -1842,14 +1881,15 @@ struct SortOut {
   uint32_t K, T;     // entries per accumulate thread, accumulate threads
 };
 
-// Digits + two-level counting sort of points [0, m) (virtual points i and, with GLV, nsplit + i)
-// into so, on stream st.  With phix set (bases resident) k_bin_hist also writes the GLV table;
+// Digits + two-level counting sort of points [0, m) (virtual points p_off + i and, with GLV,
+// nsplit + i: nsplit = m and p_off = 0 for a table of these m points, a resident set's phi record
+// base and offset otherwise) into so, on stream st.  With phix set (bases resident) k_bin_hist also writes the GLV table;
 // check_bases: Montgomery bases checked to be reduced on the way.
 static int msm_sort(const MsmPlan& p, const MsmScratch& w, const SortOut& so, const G1Aff* bases,
                     const Fr* scalars, size_t m, int mont_in, int device, hipStream_t st, uint4* phix,
                     uint32_t nsplit, int check_bases, hipEvent_t ev_sort_mid, hipStream_t side = nullptr,
                     hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr, uint32_t w0 = 0,
-                    uint32_t nw = 0, uint4* stored = nullptr) {
+                    uint32_t nw = 0, uint4* stored = nullptr, uint32_t p_off = 0) {
   const int LOGB = p.c - 1;
   const int nb = p.glv ? 128 : 255;
   const uint32_t CB = (uint32_t)coarse_bits(p.c, nb), FB = (uint32_t)LOGB - CB, NBIN = 1u << CB;
@@ -1858,8 +1898,8 @@ static int msm_sort(const MsmPlan& p, const MsmScratch& w, const SortOut& so, co
   const uint32_t npts = (uint32_t)m;  // real points (GLV: 2 m virtual ones)
   const uint32_t ep = p.glv ? 2 * p.W : p.W;
   const uint32_t nblk = cdiv(npts, sort_chunk((int)ep));
-  // u32 entries when every virtual point index (below nsplit + m with GLV, m without) fits
-  const uint64_t vmax = p.glv ? (uint64_t)nsplit + npts : (uint64_t)npts;
+  // u32 entries when every virtual point index (below nsplit + m with GLV, p_off + m without) fits
+  const uint64_t vmax = p.glv ? (uint64_t)nsplit + npts : (uint64_t)p_off + npts;
   int e32 = vmax <= (uint64_t(1) << (31 - FB)) ? 1 : 0;
   if (const char* e = getenv("SVGPU_SORT_E32")) e32 = e32 && atoi(e) != 0;
   static const int xcd = !getenv("SVGPU_SORT_XCD") || atoi(getenv("SVGPU_SORT_XCD")) != 0 ? 1 : 0;
@@ -1885,7 +1925,7 @@ static int msm_sort(const MsmPlan& p, const MsmScratch& w, const SortOut& so, co
   // measured 12 -> 122 us for that kernel: the fence writes back the XCD's L2)
   hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, st, w.btot, nwb, w.bstart, so.gst + (size_t)nw * p.B);
   SV_LAUNCH_C(k_bin_scatter, p.glv, p.c, dim3(nblk), dim3(kBlock), scalars, npts, mont_in, nblk, w.bcnt, w.btot, w.bstart,
-              w.tmp, e32, xcd, bm, w0, nw, stored);
+              w.tmp, e32, xcd, bm, w0, nw, stored, p_off, p.glv ? nsplit : 0u);
   static thread_local int fine_attr_dev = -1;  // the > 64 KiB dynamic-LDS opt-in, once per thread/device
   if (fine_attr_dev != device) {
     SV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fine_sort<0>),
@@ -2006,8 +2046,13 @@ static std::vector<size_t> piece_bounds(size_t n, int pieces, const std::vector<
   return b;
 }
 
+// res (a resident base set, msm.hpp): the call's points are rows [res->off, res->off + n) of the set.
+// Nothing is converted, checked or tabulated per call: the sorts run on the scalars alone and emit
+// the set's record indices (P at off + i, phi(P) at N + off + i), the accumulate reads the set's
+// table, a host-fed call stages scalars only, and d_bases is not used.
 static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, int form, int device,
-                        hipStream_t user_stream, const MsmFeed* feed, host::Xyzz* out) {
+                        hipStream_t user_stream, const MsmFeed* feed, host::Xyzz* out,
+                        const MsmResident* res = nullptr) {
   if (n == 0) {
     set_error("pairs should not be empty");
     return SV_ERR_EMPTY;
@@ -2030,6 +2075,16 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
   // Horner over 52 windows).  SVGPU_SMALL_MSM=0 keeps the pipeline (read per call).
   if (n <= kSmallMsmTerms && !(getenv("SVGPU_SMALL_MSM") && atoi(getenv("SVGPU_SMALL_MSM")) == 0)) {
     g_last_stats = sv_msm_stats{};
+    if (res) {  // the set's Montgomery rows
+      const void* rows = reinterpret_cast<const G1Aff*>(res->rows) + res->off;
+      const void* ds = d_scalars;
+      if (feed) {
+        SV_TRY(ws->reserve_in(Workspace::aligned(n * sizeof(Fr))));
+        SV_TRY(feed->stage_scalars(0, n, ws->inbuf, st, ws->ev[0]));
+        ds = ws->inbuf;
+      }
+      return msm_batch_windows_host(rows, ds, nullptr, 1, n, form, SV_MONTGOMERY, device, st, out);
+    }
     if (!feed) return msm_batch_windows_host(d_bases, d_scalars, nullptr, 1, n, form, form, device, st, out);
     const size_t sbytes = Workspace::aligned(n * sizeof(Fr));
     SV_TRY(ws->reserve_in(sbytes + n * sizeof(G1Aff)));
@@ -2040,6 +2095,7 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
     return msm_batch_windows_host(db, ds, nullptr, 1, n, form, form, device, st, out);
   }
   MsmPlan p = msm_plan(n);
+  if (res) p.r29 = 1;
   // host-fed inputs arrive in pieces (piece_bounds): piece k is sorted on the sort stream once its
   // scalars have landed and accumulated on the compute stream once its bases have, while later
   // pieces are still in flight
@@ -2069,7 +2125,7 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
   // 1.52 ms): k_accumulate holds two 256-thread blocks per CU, so half A's 512 blocks already fill
   // the chip and half B's wait for them -- one round of blocks each, as the whole launch's two.
   const bool split_env = getenv("SVGPU_MSM_SPLIT") && atoi(getenv("SVGPU_MSM_SPLIT")) != 0;  // per call
-  const bool split = !feed && split_env && p.W >= 2 && p.tree == 1 && n >= (size_t(1) << 16);
+  const bool split = !feed && !res && split_env && p.W >= 2 && p.tree == 1 && n >= (size_t(1) << 16);
   const uint32_t nwh[2] = {split ? p.W / 2 : p.W, split ? p.W - p.W / 2 : 0};
   uint32_t Th[2] = {0, 0};
   if (split) {
@@ -2085,10 +2141,11 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
   const uint32_t nblk = cdiv(max_piece, sort_chunk((int)ep));
   size_t bytes = 0;
   auto add = [&](size_t b) { bytes += Workspace::aligned(b); };
-  const bool conv = (form == SV_CANONICAL);
+  const bool conv = (form == SV_CANONICAL) && !res;
   if (conv) add(n * sizeof(G1Aff));
   // GLV: beta x (or phi(P)) per point; the 29-bit chain: its table of every virtual point instead
-  const size_t tab4 = p.r29 ? vtab_uint4_per_point(p.glv) : (p.glv ? (p.phi64 ? 4 : 2) : 0);  // uint4 per point
+  // (none for a resident set: the accumulate reads the set's own table)
+  const size_t tab4 = res ? 0 : p.r29 ? vtab_uint4_per_point(p.glv) : (p.glv ? (p.phi64 ? 4 : 2) : 0);  // uint4 per point
   if (tab4) add(n * tab4 * sizeof(uint4));
   const size_t nfinal = (size_t)p.W * p.NG;
   uint32_t gparts = nfinal < 256 ? 2 : 1;      // k_group_sum blocks per group (see there)
@@ -2122,12 +2179,16 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
   SV_TRY(ws->reserve(bytes));
   SV_TRY(ws->reserve_pinned(nfinal * sizeof(G1Xyzz) + 256));
   if (feed) {
-    SV_TRY(ws->reserve_in(Workspace::aligned(n * sizeof(G1Aff)) + Workspace::aligned(n * sizeof(Fr))));
+    const size_t bbytes = res ? 0 : Workspace::aligned(n * sizeof(G1Aff));
+    SV_TRY(ws->reserve_in(bbytes + Workspace::aligned(n * sizeof(Fr))));
     SV_TRY(ws->ensure_copy_stream());
     SV_TRY(ws->ensure_sort_stream());
-    d_bases = ws->inbuf;
-    d_scalars = ws->inbuf + Workspace::aligned(n * sizeof(G1Aff));
+    d_bases = res ? nullptr : ws->inbuf;
+    d_scalars = ws->inbuf + bbytes;
   }
+  // a resident set's record indices: P_i of the call at r_off + i, phi(P_i) at r_phi + i
+  const uint32_t r_off = res ? (uint32_t)res->off : 0u, r_phi = res ? (uint32_t)(res->N + res->off) : 0u;
+  const uint4* r_tab = res ? reinterpret_cast<const uint4*>(res->vtab) : nullptr;
 
   const G1Aff* bases = reinterpret_cast<const G1Aff*>(d_bases);
   const Fr* scalars = reinterpret_cast<const Fr*>(d_scalars);
@@ -2190,7 +2251,12 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
   if (!lean) SV_HIP(hipEventRecord(ev[0], st));
   SV_HIP(hipMemsetAsync(w.err, 0, nerr * 4, st));
   const uint32_t* half_gst[2] = {nullptr, nullptr};  // split: each window half's bucket starts
-  if (!feed) {
+  if (!feed && res) {
+    SV_TRY(msm_sort(p, w, so[0], nullptr, scalars, n, mont_in, device, st, nullptr, p.glv ? r_phi : ~0u, 0,
+                    detail ? ev[1] : nullptr, nullptr, nullptr, nullptr, 0, 0, stored, r_off));
+    SV_HIP(hipEventRecord(ev[2], st));
+    SV_TRY(msm_acc(p, w, so[0], nullptr, 0, st, bsum, r_tab, ~0u, ev[3], detail ? ev[4] : nullptr));
+  } else if (!feed) {
     if (conv) {
       hipLaunchKernelGGL(k_to_mont_bases, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, st, bases, bases_m, (uint32_t)n,
                          w.err);
@@ -2283,7 +2349,7 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
             if (rc != SV_OK) break;
             staged.store(2 * k + 1, std::memory_order_release);
           }
-          rc = feed->stage_bases(lo, hi, const_cast<G1Aff*>(bases) + lo, cs, ev[9 + 3 * k]);
+          if (!res) rc = feed->stage_bases(lo, hi, const_cast<G1Aff*>(bases) + lo, cs, ev[9 + 3 * k]);
           if (rc != SV_OK) break;
           staged.store(2 * k + 2, std::memory_order_release);
         }
@@ -2339,6 +2405,22 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
       uint4* phix_k = tab4 ? phix + tab4 * lo : nullptr;
       SV_TRY(wait_stage(2 * k + 1));
       SV_HIP(hipStreamWaitEvent(ss, sc_ready, 0));
+      if (res) {
+        // a resident set: no bases to wait for, the piece's accumulate is gated on its sort alone and
+        // reads the set's table at the piece's records
+        const uint32_t lo32 = (uint32_t)lo;
+        SV_TRY(msm_sort(p, w, so[k], nullptr, dsc, m, mont_in, device, ss, nullptr, p.glv ? r_phi + lo32 : ~0u, 0,
+                        nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, r_off + lo32));
+        SV_HIP(hipEventRecord(sorted, ss));
+        SV_HIP(hipStreamWaitEvent(st, sorted, 0));
+        if (k == 0) SV_HIP(hipEventRecord(ev[2], st));
+        MsmScratch wk = w;
+        wk.nheavy = w.err + 1 + 2 * k;
+        wk.nmulti = w.err + 2 + 2 * k;
+        SV_TRY(msm_acc(p, wk, so[k], nullptr, k > 0 ? 1 : 0, st, bsum, r_tab, ~0u,
+                       k == pieces - 1 ? ev[3] : nullptr, nullptr));
+        continue;
+      }
       SV_TRY(msm_sort(p, w, so[k], nullptr, dsc, m, mont_in, device, ss, nullptr, nsplit, 0, nullptr));
       if (!prep_on_sort) SV_HIP(hipEventRecord(sorted, ss));
       SV_TRY(wait_stage(2 * k + 2));
@@ -2490,6 +2572,41 @@ int msm_run_device(const void* d_bases, const void* d_scalars, size_t n, int for
 
 int msm_run_fed(size_t n, int form, int device, const MsmFeed& feed, host::Xyzz* out) {
   return msm_run_impl(nullptr, nullptr, n, form, device, nullptr, &feed, out);
+}
+
+int msm_resident_prepare(const void* d_rows, size_t n, int form, int device, hipStream_t user_stream,
+                         void* d_rows_m, void* d_vtab) {
+  WsLease lease(device, user_stream);
+  if (!lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = lease.get();
+  hipStream_t st = ws->stream;
+  SV_TRY(ws->reserve(256));
+  SV_TRY(ws->reserve_pinned(256));
+  uint32_t* err = ws->carve<uint32_t>(1);
+  SV_HIP(hipMemsetAsync(err, 0, 4, st));
+  hipLaunchKernelGGL(k_resident_prepare, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, st,
+                     reinterpret_cast<const G1Aff*>(d_rows), reinterpret_cast<G1Aff*>(d_rows_m), (uint32_t)n,
+                     form == SV_MONTGOMERY ? 1 : 0, reinterpret_cast<uint4*>(d_vtab), err);
+  SV_HIP(hipGetLastError());
+  SV_HIP(hipMemcpyAsync(ws->pinned, err, 4, hipMemcpyDeviceToHost, st));
+  SV_HIP(hipStreamSynchronize(st));
+  uint32_t errv;
+  memcpy(&errv, ws->pinned, 4);
+  if (errv) {
+    set_error("invalid input: base coordinate not reduced mod p");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+
+int msm_run_resident_device(const MsmResident& set, const void* d_scalars, size_t n, int form, int device,
+                            hipStream_t user_stream, host::Xyzz* out) {
+  return msm_run_impl(nullptr, d_scalars, n, form, device, user_stream, nullptr, out, &set);
+}
+
+int msm_run_resident_fed(const MsmResident& set, size_t n, int form, int device, const MsmFeed& feed,
+                         host::Xyzz* out) {
+  return msm_run_impl(nullptr, nullptr, n, form, device, nullptr, &feed, out, &set);
 }
 
 }  // namespace sv

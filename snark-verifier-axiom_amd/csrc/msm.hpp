@@ -55,6 +55,28 @@ struct MsmFeed {
 };
 int msm_run_fed(size_t n, int form, int device, const MsmFeed& feed, host::Xyzz* out);
 
+// Resident base set: N affine points kept on one device in the form the pipeline consumes, 208 B
+// per point -- the Montgomery rows (64 B, the small route's input) and the 29-bit chain's table of
+// 2 N records of 72 B, P_i at record i and phi(P_i) = (beta x_i, y_i) at record N + i.
+// msm_resident_prepare fills both from N rows in `form` (d_rows may equal d_rows_m) and returns
+// SV_ERR_ARG for a coordinate not below p.  The runs compute sum_i scalars[i] * set[off + i] over
+// rows [off, off + n) with the plan of n: no base is converted, checked or tabulated per call, the
+// 29-bit chain is used whatever SVGPU_ACC_R29 says, and a fed call stages scalars only
+// (feed.stage_bases is not called).
+constexpr size_t kResidentRowBytes = 64, kResidentTabBytes = 144;
+struct MsmResident {
+  const void* rows;  // N Montgomery rows
+  const void* vtab;  // 2 N table records
+  size_t N;
+  size_t off;        // first row of this call
+};
+int msm_resident_prepare(const void* d_rows, size_t n, int form, int device, hipStream_t stream, void* d_rows_m,
+                         void* d_vtab);
+int msm_run_resident_device(const MsmResident& set, const void* d_scalars, size_t n, int form, int device,
+                            hipStream_t stream, host::Xyzz* out);
+int msm_run_resident_fed(const MsmResident& set, size_t n, int form, int device, const MsmFeed& feed,
+                         host::Xyzz* out);
+
 int msm_last_stats(sv_msm_stats* out);
 
 }  // namespace sv

@@ -12,8 +12,8 @@ All compute runs in libsvgpu.so (HIP, gfx950); there is no CPU fallback.
 from ._lib import (SV_CANONICAL, SV_MONTGOMERY, ArgumentError, DeviceError, EmptyError, LengthError,
                    OutOfMemoryError, SvError, lib)
 from .kzg import AssertionFailure, KzgAccumulator, KzgAs, KzgDecidingKey
-from .loader import (BaseTable, NativeLoader, ReferencePanic, batch_multi_scalar_multiplication, fold_partials, msm_arrays,
-                     make_refs, msm_batch_arrays, msm_refs, multi_scalar_multiplication)
+from .loader import (BaseTable, NativeLoader, ReferencePanic, ResidentBases, batch_multi_scalar_multiplication,
+                     fold_partials, msm_arrays, make_refs, msm_batch_arrays, msm_refs, multi_scalar_multiplication)
 from .poseidon import Poseidon, PoseidonTranscript
 
 

@@ -111,6 +111,13 @@ PROTOTYPES = [
     ("sv_bn254_g1_table_device", c_int, [c_uint64, POINTER(c_int)]),
     ("sv_bn254_g1_msm_batch_indexed_device", c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p,
                                                       c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    ("sv_bn254_g1_bases_create", c_int, [c_void_p, c_size_t, c_int, c_int, POINTER(c_uint64)]),
+    ("sv_bn254_g1_bases_create_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p, POINTER(c_uint64)]),
+    ("sv_bn254_g1_bases_destroy", c_int, [c_uint64]),
+    ("sv_bn254_g1_bases_info", c_int, [c_uint64, POINTER(c_uint64), POINTER(c_int), POINTER(c_uint64)]),
+    ("sv_bn254_g1_msm_bases", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, c_int, POINTER(sv_g1_affine)]),
+    ("sv_bn254_g1_msm_bases_device", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, c_int, c_void_p,
+                                              POINTER(sv_g1_jacobian)]),
     ("sv_bn254_poseidon_permute", c_int, [c_void_p, c_size_t, c_int, c_int]),
     ("sv_bn254_poseidon_permute_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_squeeze", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

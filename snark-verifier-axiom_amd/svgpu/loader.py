@@ -189,6 +189,111 @@ class BaseTable:
         return self.msm_batch_arrays(np.array(idx, dtype=np.uint32), enc.scalars_array(scalars), offsets)
 
 
+class ResidentBases:
+    """A resident base set for large MSMs: the bases of a KZG MSM (the SRS, a Lagrange basis, a
+    committing key) uploaded ONCE to `device` and kept there in the form the MSM pipeline consumes
+    (208 B per point: Montgomery rows + the accumulate's 29-bit table of P and phi(P)), so each MSM
+    ships only its scalars and prepares no base.  `bases`: an (n, 8) u64 array in `form`, or a
+    sequence of points.  One set lives on one device; with several GPUs make one set per device
+    over its shard and fold the partials (fold_partials)."""
+
+    def __init__(self, bases, device: int = 0, form: int = _lib.SV_CANONICAL):
+        self.handle = None
+        if not isinstance(bases, np.ndarray):
+            bases = enc.bases_array(list(bases))
+        arr = np.ascontiguousarray(bases, dtype=np.uint64)
+        h = ctypes.c_uint64(0)
+        _lib.check(_lib.lib.sv_bn254_g1_bases_create(arr.ctypes.data, arr.shape[0], form, device, ctypes.byref(h)),
+                   "sv_bn254_g1_bases_create")
+        self.handle = h.value
+        self._info()
+
+    @classmethod
+    def from_device(cls, tensor, form: int = _lib.SV_MONTGOMERY) -> "ResidentBases":
+        """A set over rows already in HBM: an (n, 8) int64 torch tensor in `form`; the set lives on the
+        tensor's device and keeps its own copy (the tensor may be freed afterwards)."""
+        import torch
+        if tensor.device.type != "cuda":
+            raise _lib.DeviceError("tensor must live on a GPU (cuda/HIP device)")
+        tensor = tensor.contiguous()
+        d = tensor.device.index if tensor.device.index is not None else torch.cuda.current_device()
+        self = cls.__new__(cls)
+        self.handle = None
+        h = ctypes.c_uint64(0)
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        _lib.check(_lib.lib.sv_bn254_g1_bases_create_device(tensor.data_ptr(), tensor.shape[0], form, d, stream,
+                                                            ctypes.byref(h)), "sv_bn254_g1_bases_create_device")
+        self.handle = h.value
+        self._info()
+        return self
+
+    def _info(self):
+        n, d, b = ctypes.c_uint64(0), ctypes.c_int(-1), ctypes.c_uint64(0)
+        _lib.check(_lib.lib.sv_bn254_g1_bases_info(self.handle, ctypes.byref(n), ctypes.byref(d), ctypes.byref(b)),
+                   "sv_bn254_g1_bases_info")
+        self.n, self.device, self.device_bytes = n.value, d.value, b.value
+
+    def close(self):
+        if self.handle is not None:
+            h, self.handle = self.handle, None
+            _lib.check(_lib.lib.sv_bn254_g1_bases_destroy(h), "sv_bn254_g1_bases_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def msm_arrays(self, scalars: np.ndarray, offset: int = 0, form: int = _lib.SV_CANONICAL) -> Point:
+        """sum_i scalars[i] * set[offset + i] over host scalars ((n, 4) u64 in `form`)."""
+        if self.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+        out = _lib.sv_g1_affine()
+        rc = _lib.lib.sv_bn254_g1_msm_bases(self.handle, offset, scalars.ctypes.data, scalars.shape[0], form,
+                                            ctypes.byref(out))
+        if rc == _lib.SV_ERR_EMPTY:
+            raise ReferencePanic("pairs should not be empty")
+        _lib.check(rc, "sv_bn254_g1_msm_bases")
+        return enc.g1_from_struct(out, form)
+
+    def _partial_struct(self, scalars, offset: int, form: int):
+        import torch
+        if self.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        if scalars.device.type != "cuda":
+            raise _lib.DeviceError("tensor must live on a GPU (cuda/HIP device)")
+        part = _lib.sv_g1_jacobian()
+        stream = torch.cuda.current_stream(scalars.device).cuda_stream
+        rc = _lib.lib.sv_bn254_g1_msm_bases_device(self.handle, offset, scalars.data_ptr(), scalars.shape[0], form,
+                                                   stream, ctypes.byref(part))
+        if rc == _lib.SV_ERR_EMPTY:
+            raise ReferencePanic("pairs should not be empty")
+        _lib.check(rc, "sv_bn254_g1_msm_bases_device")
+        return part
+
+    def msm_device_partial(self, scalars, offset: int = 0, form: int = _lib.SV_MONTGOMERY) -> Tuple[int, int, int]:
+        """sum_i scalars[i] * set[offset + i] over scalars in HBM on the set's device ((n, 4) int64
+        torch tensor in `form`) -> canonical Jacobian partial (X, Y, Z), the value to fold across
+        devices (fold_partials)."""
+        return enc.jacobian_from_struct(self._partial_struct(scalars, offset, form))
+
+    def msm_device(self, scalars, offset: int = 0, form: int = _lib.SV_MONTGOMERY) -> Point:
+        """The same as an affine point (canonical ints; None = identity): the partial goes straight
+        into sv_bn254_g1_fold."""
+        part = self._partial_struct(scalars, offset, form)
+        out = _lib.sv_g1_affine()
+        _lib.check(_lib.lib.sv_bn254_g1_fold(ctypes.byref(part), 1, ctypes.byref(out), _lib.SV_CANONICAL),
+                   "sv_bn254_g1_fold")
+        return enc.g1_from_struct(out)
+
+
 def batch_multi_scalar_multiplication(msms: Sequence[Sequence[Tuple[int, Point]]]) -> list:
     """[NativeLoader.multi_scalar_multiplication(pairs) for pairs in msms], one GPU launch."""
     offsets = [0]

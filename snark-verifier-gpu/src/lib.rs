@@ -140,6 +140,16 @@ extern "C" {
                                                 d_offsets: *const u64, count: usize, max_terms: usize,
                                                 form: c_int, device: c_int, stream: *mut c_void,
                                                 d_out: *mut SvG1Affine) -> c_int;
+    pub fn sv_bn254_g1_bases_create(bases: *const SvG1Affine, n: usize, form: c_int, device: c_int,
+                                    handle: *mut u64) -> c_int;
+    pub fn sv_bn254_g1_bases_create_device(d_bases: *const SvG1Affine, n: usize, form: c_int, device: c_int,
+                                           stream: *mut c_void, handle: *mut u64) -> c_int;
+    pub fn sv_bn254_g1_bases_destroy(handle: u64) -> c_int;
+    pub fn sv_bn254_g1_bases_info(handle: u64, n: *mut u64, device: *mut c_int, device_bytes: *mut u64) -> c_int;
+    pub fn sv_bn254_g1_msm_bases(handle: u64, offset: usize, scalars: *const SvFe, n: usize, form: c_int,
+                                 out: *mut SvG1Affine) -> c_int;
+    pub fn sv_bn254_g1_msm_bases_device(handle: u64, offset: usize, d_scalars: *const SvFe, n: usize,
+                                        form: c_int, stream: *mut c_void, out_partial: *mut SvG1Jacobian) -> c_int;
     pub fn sv_bn254_poseidon_permute(states: *mut SvFe, n: usize, t: c_int, form: c_int) -> c_int;
     pub fn sv_bn254_poseidon_permute_device(d_states: *mut SvFe, n: usize, t: c_int, form: c_int, device: c_int,
                                             stream: *mut c_void) -> c_int;
@@ -439,6 +449,64 @@ impl Drop for BaseTable {
     fn drop(&mut self) {
         unsafe {
             sv_bn254_g1_table_destroy(self.handle);
+        }
+    }
+}
+
+/// A resident base set for large MSMs: fixed bases (the SRS, a Lagrange basis, a committing key)
+/// uploaded once to one device and kept there in the form the MSM pipeline consumes, so every MSM
+/// ships only its scalars.  One set lives on one device (no multi-device handle): with several
+/// GPUs make one set per device over its shard and fold the partials (`sv_bn254_g1_fold`).
+pub struct ResidentBases {
+    handle: u64,
+    n: usize,
+}
+
+impl ResidentBases {
+    pub fn new(bases: &[G1Affine], device: i32) -> Option<Self> {
+        let mut handle = 0u64;
+        let rc = unsafe {
+            sv_bn254_g1_bases_create(bases.as_ptr() as *const SvG1Affine, bases.len(), SV_MONTGOMERY, device,
+                                     &mut handle)
+        };
+        (rc == SV_OK).then_some(ResidentBases { handle, n: bases.len() })
+    }
+
+    pub fn len(&self) -> usize {
+        self.n
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.n == 0
+    }
+
+    /// Bytes the set holds on its device.
+    pub fn device_bytes(&self) -> Option<u64> {
+        let mut bytes = 0u64;
+        let rc = unsafe {
+            sv_bn254_g1_bases_info(self.handle, std::ptr::null_mut(), std::ptr::null_mut(), &mut bytes)
+        };
+        (rc == SV_OK).then_some(bytes)
+    }
+
+    /// Σ scalars[i] · set[offset + i]; panics on an empty MSM like the reference (native.rs:69).
+    pub fn msm(&self, offset: usize, scalars: &[Fr]) -> Option<G1Affine> {
+        if scalars.is_empty() {
+            panic!("pairs should not be empty");
+        }
+        let mut out = SvG1Affine::default();
+        let rc = unsafe {
+            sv_bn254_g1_msm_bases(self.handle, offset, scalars.as_ptr() as *const SvFe, scalars.len(),
+                                  SV_MONTGOMERY, &mut out)
+        };
+        (rc == SV_OK).then(|| g1_out(out))
+    }
+}
+
+impl Drop for ResidentBases {
+    fn drop(&mut self) {
+        unsafe {
+            sv_bn254_g1_bases_destroy(self.handle);
         }
     }
 }
