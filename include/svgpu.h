@@ -223,6 +223,41 @@ int sv_bn254_g1_msm_bases(uint64_t handle, size_t offset, const sv_fe* scalars, 
 int sv_bn254_g1_msm_bases_device(uint64_t handle, size_t offset, const sv_fe* d_scalars, size_t n,
                                  int form, void* stream, sv_g1_jacobian* out_partial) SV_NOEXCEPT;
 
+/* ---- KZG opening on a resident base set ------------------------------------------------
+ * The step between a commit (sv_bn254_g1_msm_bases over the coefficients) and sv_bn254_kzg_decide:
+ * for p(X) = sum_{i<n} a_i X^i and a point z, the quotient q = (p - p(z)) / (X - z) and the witness
+ * sum_{i<n-1} q_i set[offset + i], with the division on the device (a three-launch suffix scan over
+ * Fr, csrc/kzg_open.hip) and the witness through the resident MSM pipeline, so coefficients that are
+ * already in HBM never travel to the host.  With the suffix Horner values h_i = a_i + z h_{i+1}:
+ * p(z) = h_0 and q_i = h_{i+1}, all mod r, so every output is determined bit for bit.  For a set
+ * set[i] = s^i g and the commitment C of p over it, lhs = C - p(z) g + z witness, rhs = witness is
+ * an accumulator that sv_bn254_kzg_decide accepts under (g, g2, s g2).
+ * fr_poly_div_linear_device: the division alone.  d_coeffs (n elements) and d_quotient (n - 1
+ *   elements, `form`; may be NULL = evaluate only; overlapping d_coeffs is SV_ERR_ARG) are in HBM
+ *   on `device` (as for sv_bn254_g1_msm_device), `stream` may be NULL; z and out_eval are host
+ *   pointers; synchronous on `stream`.
+ * kzg_open / kzg_open_device: coefficients on the host (one transfer) or in HBM on the set's
+ *   device; the quotient lives in pooled scratch in Montgomery form and feeds the set's MSM on the
+ *   same stream (sv_msm_last_stats reflects that MSM).  `form` covers the coefficients, z, the
+ *   evaluation and the affine witness; the Jacobian partial is canonical, as for
+ *   sv_bn254_g1_msm_bases_device.  n == 1 is legal: the evaluation is a_0, the witness the identity,
+ *   and no MSM runs; an all-zero quotient gives the identity too.
+ * Checked before any device work, in this order: bad form or null pointer SV_ERR_ARG, n == 0
+ * SV_ERR_EMPTY, n > 2^26 SV_ERR_LEN, z not below r SV_ERR_ARG ("not reduced"), unknown or destroyed
+ * handle SV_ERR_ARG, offset + (n - 1) beyond the set SV_ERR_ARG.  A coefficient not below r is
+ * SV_ERR_ARG ("not reduced") for that call, found on the device; the handle stays usable.  Calls
+ * are re-entrant on one handle like the other resident calls.
+ * Not covered: host coefficients fed in pieces, high end first, so that the copy overlaps the scan
+ * and the sort; several polynomials or several points per call; multi-device sets.              */
+int sv_bn254_fr_poly_div_linear_device(const sv_fe* d_coeffs, size_t n, const sv_fe* z, int form,
+                                       int device, void* stream, sv_fe* d_quotient,
+                                       sv_fe* out_eval) SV_NOEXCEPT;
+int sv_bn254_kzg_open(uint64_t handle, size_t offset, const sv_fe* coeffs, size_t n, const sv_fe* z,
+                      int form, sv_fe* out_eval, sv_g1_affine* out_witness) SV_NOEXCEPT;
+int sv_bn254_kzg_open_device(uint64_t handle, size_t offset, const sv_fe* d_coeffs, size_t n,
+                             const sv_fe* z, int form, void* stream, sv_fe* out_eval,
+                             sv_g1_jacobian* out_witness_partial) SV_NOEXCEPT;
+
 /* ---- Poseidon sponge over BN254 Fr --------------------------
  * x^5 HADES permutation, width t = 3 (R_F 8, R_P 57, rate 2: the SDK's PoseidonTranscript,
  * snark-verifier-sdk/src/halo2.rs:52-71) or t = 5 (R_F 8, R_P 60, rate 4).  States are t

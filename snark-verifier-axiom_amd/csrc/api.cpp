@@ -20,6 +20,7 @@
 #include "gen.hpp"
 #include "host_ec.hpp"
 #include "host_poseidon.hpp"
+#include "kzg_open.hpp"
 #include "msm.hpp"
 #include "msm_batch.hpp"
 #include "poseidon.hpp"
@@ -1079,6 +1080,147 @@ int sv_bn254_g1_msm_bases_device(uint64_t handle, size_t offset, const sv_fe* d_
   Xyzz r;
   SV_TRY(msm_run_resident_device(set, d_scalars, n, form, t.dev, (hipStream_t)stream, &r));
   jacobian_out(r, out_partial);
+  return SV_OK;
+  SV_GUARD_END
+}
+
+// ---- KZG opening on a resident base set (division on the device, witness through the set's MSM) ----
+namespace {
+// the division's and the openings' checks up to z, in order: form / null, empty, length, z (no
+// device touched); d_quotient is not among the pointers (NULL = evaluate only)
+int div_call_args(const void* coeffs, size_t n, const sv_fe* z, int form, const void* out_eval, const void* out) {
+  SV_TRY(check_form(form));
+  if (!coeffs || !z || !out_eval || !out) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (n == 0) {
+    sv::set_error("polynomial should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (n > kMaxSetRows) {
+    sv::set_error("n = %zu exceeds the per-device limit 2^26", n);
+    return SV_ERR_LEN;
+  }
+  if (!host::f_is_reduced(fe_in(*z), host::R64)) {
+    sv::set_error("z not reduced mod the scalar field order");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+
+// then the handle and the range of the n - 1 quotient terms (offset + (n - 1) > N without the sum)
+int open_call_args(uint64_t handle, size_t offset, const void* coeffs, size_t n, const sv_fe* z, int form,
+                   const void* out_eval, const void* out, BaseSet* t) {
+  SV_TRY(div_call_args(coeffs, n, z, form, out_eval, out));
+  if (!set_lookup(handle, t)) return SV_ERR_ARG;
+  if (offset > t->n || n - 1 > t->n - offset) {
+    sv::set_error("rows [%zu, %zu + %zu) reach past base set %llu (%zu rows)", offset, offset, n - 1,
+                  (unsigned long long)handle, t->n);
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+
+// A leased workspace whose stream is drained before the lease goes back to the pool, whatever the
+// exit path: the division's kernels and copies may still be in flight on an early error return.
+struct DrainedLease {
+  WsLease lease;
+  bool armed = true;
+  DrainedLease(int device, hipStream_t stream) : lease(device, stream) {}
+  ~DrainedLease() {
+    if (armed && lease.ok()) (void)hipStreamSynchronize(lease.get()->stream);
+  }
+  Workspace* ws() { return lease.get(); }
+};
+
+// the division's head (kzg_open.hpp) once the stream has drained: the error flag, then p(z)
+int div_result(const char* head, sv_fe* out_eval) {
+  uint32_t errv;
+  memcpy(&errv, head + kDivErrOffset, 4);
+  if (errv) {
+    sv::set_error("invalid input: coefficient not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  memcpy(out_eval->l, head + kDivEvalOffset, sizeof(sv_fe));
+  return SV_OK;
+}
+
+// Both openings: coefficients from the host (one transfer into the pooled input buffer) or in HBM,
+// the quotient into pooled scratch in Montgomery form, the set's MSM over it on the same stream.
+int open_run(const BaseSet& t, size_t offset, const sv_fe* coeffs, bool from_device, size_t n, const sv_fe* z,
+             int form, hipStream_t stream, sv_fe* out_eval, Xyzz* witness) {
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(t.dev, stream);
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  const size_t cbytes = from_device ? 0 : Workspace::aligned(n * sizeof(sv_fe));
+  SV_TRY(ws->reserve_in(cbytes + Workspace::aligned((n - 1) * sizeof(sv_fe) + 1)));
+  SV_TRY(ws->reserve(poly_div_scratch_bytes(n)));
+  SV_TRY(ws->reserve_pinned(kDivHeadBytes));
+  const void* d_coeffs = coeffs;
+  if (!from_device) {
+    SV_HIP(hipMemcpyAsync(ws->inbuf, coeffs, n * sizeof(sv_fe), hipMemcpyHostToDevice, ws->stream));
+    d_coeffs = ws->inbuf;
+  }
+  void* d_quot = ws->inbuf + cbytes;
+  SV_TRY(poly_div_linear_enqueue(d_coeffs, n, *z, form, SV_MONTGOMERY, d_quot, ws->buf, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned, ws->buf, kDivHeadBytes, hipMemcpyDeviceToHost, ws->stream));
+  *witness = host::x_identity();
+  if (n > 1) {  // the MSM synchronises the stream, so the head has landed when it returns
+    const MsmResident set{t.rows, t.vtab, t.n, offset};
+    SV_TRY(msm_run_resident_device(set, d_quot, n - 1, SV_MONTGOMERY, t.dev, ws->stream, witness));
+  } else {
+    SV_HIP(hipStreamSynchronize(ws->stream));
+  }
+  dl.armed = false;
+  return div_result(ws->pinned, out_eval);
+}
+}  // namespace
+
+int sv_bn254_fr_poly_div_linear_device(const sv_fe* d_coeffs, size_t n, const sv_fe* z, int form, int device,
+                                       void* stream, sv_fe* d_quotient, sv_fe* out_eval) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(div_call_args(d_coeffs, n, z, form, out_eval, out_eval));
+  const uintptr_t cb = (uintptr_t)d_coeffs, qb = (uintptr_t)d_quotient;
+  if (d_quotient && qb < cb + n * sizeof(sv_fe) && cb < qb + (n - 1) * sizeof(sv_fe)) {
+    sv::set_error("d_quotient overlaps d_coeffs (phase 3 reads the coefficients again while it writes)");
+    return SV_ERR_ARG;
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, (hipStream_t)stream);
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  SV_TRY(ws->reserve(poly_div_scratch_bytes(n)));
+  SV_TRY(ws->reserve_pinned(kDivHeadBytes));
+  SV_TRY(poly_div_linear_enqueue(d_coeffs, n, *z, form, form, d_quotient, ws->buf, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned, ws->buf, kDivHeadBytes, hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl.armed = false;
+  return div_result(ws->pinned, out_eval);
+  SV_GUARD_END
+}
+
+int sv_bn254_kzg_open(uint64_t handle, size_t offset, const sv_fe* coeffs, size_t n, const sv_fe* z, int form,
+                      sv_fe* out_eval, sv_g1_affine* out_witness) noexcept {
+  SV_GUARD_BEGIN
+  BaseSet t;
+  SV_TRY(open_call_args(handle, offset, coeffs, n, z, form, out_eval, out_witness, &t));
+  Xyzz w;
+  SV_TRY(open_run(t, offset, coeffs, false, n, z, form, nullptr, out_eval, &w));
+  affine_out(w, form, out_witness);
+  return SV_OK;
+  SV_GUARD_END
+}
+
+int sv_bn254_kzg_open_device(uint64_t handle, size_t offset, const sv_fe* d_coeffs, size_t n, const sv_fe* z,
+                             int form, void* stream, sv_fe* out_eval, sv_g1_jacobian* out_witness_partial) noexcept {
+  SV_GUARD_BEGIN
+  BaseSet t;
+  SV_TRY(open_call_args(handle, offset, d_coeffs, n, z, form, out_eval, out_witness_partial, &t));
+  Xyzz w;
+  SV_TRY(open_run(t, offset, d_coeffs, true, n, z, form, (hipStream_t)stream, out_eval, &w));
+  jacobian_out(w, out_witness_partial);
   return SV_OK;
   SV_GUARD_END
 }

@@ -23,5 +23,11 @@ def init(num_devices: int = 0) -> int:
     return lib.sv_device_count()
 
 
+def poly_div_linear_device(coeffs, z, **kwargs):
+    """svgpu.device.poly_div_linear_device (imported on first use: that module needs torch)."""
+    from .device import poly_div_linear_device as run
+    return run(coeffs, z, **kwargs)
+
+
 def version() -> str:
     return lib.sv_version().decode()

@@ -118,6 +118,12 @@ PROTOTYPES = [
     ("sv_bn254_g1_msm_bases", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, c_int, POINTER(sv_g1_affine)]),
     ("sv_bn254_g1_msm_bases_device", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, c_int, c_void_p,
                                               POINTER(sv_g1_jacobian)]),
+    ("sv_bn254_fr_poly_div_linear_device", c_int, [c_void_p, c_size_t, POINTER(sv_fe), c_int, c_int, c_void_p,
+                                                    c_void_p, POINTER(sv_fe)]),
+    ("sv_bn254_kzg_open", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, POINTER(sv_fe), c_int, POINTER(sv_fe),
+                                   POINTER(sv_g1_affine)]),
+    ("sv_bn254_kzg_open_device", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, POINTER(sv_fe), c_int, c_void_p,
+                                          POINTER(sv_fe), POINTER(sv_g1_jacobian)]),
     ("sv_bn254_poseidon_permute", c_int, [c_void_p, c_size_t, c_int, c_int]),
     ("sv_bn254_poseidon_permute_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_squeeze", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

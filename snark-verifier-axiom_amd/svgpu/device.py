@@ -76,6 +76,27 @@ def msm(bases: torch.Tensor, scalars: torch.Tensor, form: int = _lib.SV_MONTGOME
     return enc.g1_from_struct(out)
 
 
+def poly_div_linear_device(coeffs: torch.Tensor, z: int, form: int = _lib.SV_MONTGOMERY, quotient: bool = True,
+                           out: torch.Tensor = None) -> Tuple[int, Optional[torch.Tensor]]:
+    """(p - p(z)) / (X - z) for the HBM-resident coefficients of p ((n, 4) int64 limbs in `form`; z a
+    canonical int) -> (p(z) as a canonical int, the n - 1 quotient coefficients in `form`, or None
+    with quotient=False: evaluate only).  `out` (at least n - 1 rows) must not overlap coeffs."""
+    d = _dev_index(coeffs)
+    coeffs = coeffs.contiguous()
+    n = coeffs.shape[0]
+    if quotient and out is None:
+        out = torch.empty((max(n - 1, 1), 4), dtype=torch.int64, device=coeffs.device)
+    elif quotient and (out.device != coeffs.device or out.dtype != torch.int64 or not out.is_contiguous()
+                       or out.dim() != 2 or out.shape[1] != 4 or out.shape[0] < n - 1):
+        raise _lib.LengthError(f"poly_div: out must be a contiguous (>= {n - 1}, 4) int64 tensor on {coeffs.device}")
+    zs, ev = enc.fr_struct(z, form), _lib.sv_fe()
+    _lib.check(_lib.lib.sv_bn254_fr_poly_div_linear_device(coeffs.data_ptr(), n, ctypes.byref(zs), form, d,
+                                                           _stream_handle(coeffs.device),
+                                                           out.data_ptr() if quotient else None, ctypes.byref(ev)),
+               "sv_bn254_fr_poly_div_linear_device")
+    return enc.fr_from_struct(ev, form), (out[:n - 1] if quotient else None)
+
+
 def last_msm_stats() -> dict:
     s = _lib.sv_msm_stats()
     _lib.check(_lib.lib.sv_msm_last_stats(ctypes.byref(s)), "sv_msm_last_stats")

@@ -82,6 +82,18 @@ def fe_struct(x: int) -> _lib.sv_fe:
     return s
 
 
+def fr_struct(x: int, form: int = _lib.SV_CANONICAL) -> _lib.sv_fe:
+    """An Fr value (canonical int) as an element in `form`.  A value that is not below r goes in as
+    it is, so that the library's own check rejects it."""
+    if not 0 <= x <= _MASK256:
+        raise _lib.ArgumentError("field element out of range (0 <= x < 2^256)")
+    return fe_struct(_to_form(x, R, form) if x < R else x)
+
+
+def fr_from_struct(a: _lib.sv_fe, form: int = _lib.SV_CANONICAL) -> int:
+    return _from_form(limbs_to_int(list(a.l)), R, form)
+
+
 def g1_struct(pt, form: int = _lib.SV_CANONICAL) -> _lib.sv_g1_affine:
     s = _lib.sv_g1_affine()
     if pt is not None:

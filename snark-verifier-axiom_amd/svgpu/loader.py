@@ -294,6 +294,40 @@ class ResidentBases:
         return enc.g1_from_struct(out)
 
 
+    def open_arrays(self, coeffs: np.ndarray, z: int, offset: int = 0,
+                    form: int = _lib.SV_CANONICAL) -> Tuple[int, Point]:
+        """KZG opening of p(X) = sum_i coeffs[i] X^i at z over set[offset:]: host coefficients
+        ((n, 4) u64 in `form`), z a canonical int -> (p(z), witness), both canonical
+        (sv_bn254_kzg_open: the division and the witness MSM run on the device)."""
+        if self.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        zs, ev, out = enc.fr_struct(z, form), _lib.sv_fe(), _lib.sv_g1_affine()
+        _lib.check(_lib.lib.sv_bn254_kzg_open(self.handle, offset, coeffs.ctypes.data, coeffs.shape[0],
+                                              ctypes.byref(zs), form, ctypes.byref(ev), ctypes.byref(out)),
+                   "sv_bn254_kzg_open")
+        return enc.fr_from_struct(ev, form), enc.g1_from_struct(out, form)
+
+    def open_device(self, coeffs, z: int, offset: int = 0, form: int = _lib.SV_MONTGOMERY) -> Tuple[int, Point]:
+        """The same for coefficients in HBM on the set's device ((n, 4) int64 torch tensor in `form`):
+        they never leave the device (sv_bn254_kzg_open_device; the partial is folded on the host)."""
+        import torch
+        if self.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        if coeffs.device.type != "cuda":
+            raise _lib.DeviceError("tensor must live on a GPU (cuda/HIP device)")
+        coeffs = coeffs.contiguous()
+        zs, ev, part = enc.fr_struct(z, form), _lib.sv_fe(), _lib.sv_g1_jacobian()
+        stream = torch.cuda.current_stream(coeffs.device).cuda_stream
+        _lib.check(_lib.lib.sv_bn254_kzg_open_device(self.handle, offset, coeffs.data_ptr(), coeffs.shape[0],
+                                                     ctypes.byref(zs), form, stream, ctypes.byref(ev),
+                                                     ctypes.byref(part)), "sv_bn254_kzg_open_device")
+        out = _lib.sv_g1_affine()
+        _lib.check(_lib.lib.sv_bn254_g1_fold(ctypes.byref(part), 1, ctypes.byref(out), _lib.SV_CANONICAL),
+                   "sv_bn254_g1_fold")
+        return enc.fr_from_struct(ev, form), enc.g1_from_struct(out)
+
+
 def batch_multi_scalar_multiplication(msms: Sequence[Sequence[Tuple[int, Point]]]) -> list:
     """[NativeLoader.multi_scalar_multiplication(pairs) for pairs in msms], one GPU launch."""
     offsets = [0]

@@ -150,6 +150,14 @@ extern "C" {
                                  out: *mut SvG1Affine) -> c_int;
     pub fn sv_bn254_g1_msm_bases_device(handle: u64, offset: usize, d_scalars: *const SvFe, n: usize,
                                         form: c_int, stream: *mut c_void, out_partial: *mut SvG1Jacobian) -> c_int;
+    pub fn sv_bn254_fr_poly_div_linear_device(d_coeffs: *const SvFe, n: usize, z: *const SvFe, form: c_int,
+                                              device: c_int, stream: *mut c_void, d_quotient: *mut SvFe,
+                                              out_eval: *mut SvFe) -> c_int;
+    pub fn sv_bn254_kzg_open(handle: u64, offset: usize, coeffs: *const SvFe, n: usize, z: *const SvFe,
+                             form: c_int, out_eval: *mut SvFe, out_witness: *mut SvG1Affine) -> c_int;
+    pub fn sv_bn254_kzg_open_device(handle: u64, offset: usize, d_coeffs: *const SvFe, n: usize, z: *const SvFe,
+                                    form: c_int, stream: *mut c_void, out_eval: *mut SvFe,
+                                    out_witness_partial: *mut SvG1Jacobian) -> c_int;
     pub fn sv_bn254_poseidon_permute(states: *mut SvFe, n: usize, t: c_int, form: c_int) -> c_int;
     pub fn sv_bn254_poseidon_permute_device(d_states: *mut SvFe, n: usize, t: c_int, form: c_int, device: c_int,
                                             stream: *mut c_void) -> c_int;
@@ -500,6 +508,20 @@ impl ResidentBases {
                                   SV_MONTGOMERY, &mut out)
         };
         (rc == SV_OK).then(|| g1_out(out))
+    }
+
+    /// KZG opening of p(X) = Σ coeffs[i] · X^i at z over set[offset..]: (p(z), witness) with
+    /// witness = Σ q_i · set[offset + i] for q = (p − p(z)) / (X − z).  The division and the MSM
+    /// run on the device; a one-coefficient polynomial gives the identity witness.
+    pub fn open(&self, offset: usize, coeffs: &[Fr], z: &Fr) -> Option<(Fr, G1Affine)> {
+        let mut eval = Fr::zero();
+        let mut out = SvG1Affine::default();
+        let rc = unsafe {
+            sv_bn254_kzg_open(self.handle, offset, coeffs.as_ptr() as *const SvFe, coeffs.len(),
+                              z as *const Fr as *const SvFe, SV_MONTGOMERY, &mut eval as *mut Fr as *mut SvFe,
+                              &mut out)
+        };
+        (rc == SV_OK).then(|| (eval, g1_out(out)))
     }
 }
 
