@@ -55,9 +55,11 @@
 
 namespace sv {
 
-static constexpr int kBlock = 256;
+// (kBlock and the other constants the host's buffer sizes depend on: msm_plan.hpp)
 #ifndef SV_ACC_PREFETCH
-#define SV_ACC_PREFETCH 1  // next entry index loaded a step ahead (0: none, 2: next point too -- 162 VGPRs, no gain)
+// next entry index loaded a step ahead.  0 (none) and 2 (next point too -- 162 VGPRs, no gain) apply
+// to the 32-bit chain only: the 29-bit chain is written for 1 (the static_assert in k_accumulate)
+#define SV_ACC_PREFETCH 1
 #endif
 
 __device__ __forceinline__ G1Aff load_aff(const G1Aff* __restrict__ a, uint32_t i) {
@@ -118,8 +120,7 @@ __device__ __forceinline__ void store_xyzz(G1Xyzz* __restrict__ a, uint32_t i, c
 // ZZ and stores X, Y, ZZZ as they were), so st_rec29 / ld_rec29 move the limbs as they are and every
 // reader tests ZZ alone (r29::is_identity; tests/f29_cases.py's garbage-identity cases).
 // Arrays stay typed G1Xyzz*: rec_at gives record i of either form.
-constexpr uint32_t kRec29Words = 4 * r29::L;  // 36
-__host__ __device__ __forceinline__ size_t bucket_rec_bytes(int r29) { return r29 ? 4 * kRec29Words : sizeof(G1Xyzz); }
+// (kRec29Words, bucket_rec_bytes: msm_plan.hpp)
 template <class T>
 __host__ __device__ __forceinline__ T* rec_at(T* base, size_t i, int r29) {
   using U = typename std::conditional<std::is_const<T>::value, const uint32_t, uint32_t>::type;
@@ -388,9 +389,7 @@ __device__ __forceinline__ void ld_rec29(const uint2* __restrict__ o, r29::F& x,
   y.v[0] = q[4].y, y.v[1] = q[5].x, y.v[2] = q[5].y, y.v[3] = q[6].x, y.v[4] = q[6].y, y.v[5] = q[7].x;
   y.v[6] = q[7].y, y.v[7] = q[8].x, y.v[8] = q[8].y;
 }
-// uint4 per point of the r29 table (its buffer is carved in uint4): GLV two 72-B records, else one
-// (padded to 80 B per point so host-fed pieces' table slices stay uint4-aligned)
-__host__ __device__ constexpr size_t vtab_uint4_per_point(bool glv) { return glv ? 9 : 5; }
+// (uint4 per point of the table: vtab_uint4_per_point, msm_plan.hpp)
 __device__ __forceinline__ void vtab_put_pt(const G1Aff& a, uint32_t i, uint4* __restrict__ vtab, uint32_t nsplit,
                                             bool glv, uint32_t* __restrict__ err) {
   if (err && (!a.x.is_reduced() || !a.y.is_reduced())) atomicOr(err, 1u);
@@ -470,21 +469,8 @@ __global__ void k_check_bases(const G1Aff* __restrict__ bases, uint32_t n, uint3
 // (window, bin) counting-sorts its ~n / NBIN entries by fine index inside that bin's region (L2
 // resident), writes ent[], the global bucket offsets gst[] and the owner bucket tstart[t] of every
 // accumulate chunk [tK, tK + K).  No per-(window, point) digit array is ever stored.
-// points per block in passes 1 and 3: sort_chunk (below), 256 when the LDS staging of W digits per
-// point would not fit (small c, many windows)
-// Points per block of the histogram / scatter passes (ep: entries per point).  1024 (round 3) halves
-// the block count, so each (window, bin) run a scatter block writes is ~16 entries (64 B) instead of
-// ~8: sort 0.221 -> 0.206 ms at 2^20.  LDS: the scatter stages CH * ep u32 entries (2048 spilled
-// the scatter's digit registers: 336 B scratch, one wave per SIMD).
-#ifndef SV_SORT_CHUNK
-#define SV_SORT_CHUNK 1024
-#endif
-__host__ __device__ constexpr uint32_t sort_chunk(int ep) {
-  return ep > 20 ? 256u : (ep > 16 && SV_SORT_CHUNK > 1024 ? 1024u : (uint32_t)SV_SORT_CHUNK);
-}
-// coarse bits: 2^CB bins per window, so that W * 2^CB ~ 1024 fine-sort regions of ~16K entries at
-// 2^20 (LDS-staged in k_fine_sort) -- 64 bins for the 16 full-width windows, 128 for the 8 GLV ones
-__host__ __device__ constexpr int coarse_bits(int c, int nb) { return c - 1 < (nb == 128 ? 7 : 6) ? c - 1 : (nb == 128 ? 7 : 6); }
+// points per block in passes 1 and 3: sort_chunk (msm_plan.hpp, with coarse_bits), 256 when the LDS
+// staging of W digits per point would not fit (small c, many windows)
 __host__ __device__ constexpr int ceil_log2(int x) { return x <= 1 ? 0 : 1 + ceil_log2((x + 1) / 2); }
 
 // exclusive scan of x[0 .. N) in LDS by a 256-thread block (N <= 4096); returns the total
@@ -1487,9 +1473,8 @@ __global__ void __launch_bounds__(kGroupBlock) k_group_sum_q(const G1Xyzz* __res
 // k_group_fin then sums them per window: A over the blocks (two halves, the A_lo / A_hi slots the
 // host Horner expects), U_k (k < 8) over the blocks, U_k (k >= 8) over the blocks whose index has
 // bit k - 8 set (their CT).
-static constexpr int kTreeLog = 8, kTreeN = 1 << kTreeLog;  // segments per block (= threads)
+// kTreeN segments per block (= threads), kTreeOut per-block outputs: msm_plan.hpp
 static constexpr int kTreeRS = kTreeN + 1;                  // LDS row stride in dwords (quads conflict-free)
-static constexpr int kTreeOut = 2 + kTreeLog;               // per-block outputs
 static constexpr size_t kTreeRow = (size_t)32 * kTreeRS * 4;  // one row of 256 points, structure of arrays
 
 // dword d of point p at row[d * kTreeRS + p]; the quad form reads coordinate c (dwords 8c .. 8c + 7)
@@ -1702,106 +1687,18 @@ __global__ void __launch_bounds__(128) k_group_fin(const G1Xyzz* __restrict__ bl
 }
 
 // ---------------------------------------------------------------------------------------------
-// host orchestration
+// host orchestration (the plan, the switches, the buffer layout and the event slots: msm_plan.hpp)
 // ---------------------------------------------------------------------------------------------
+static_assert(sizeof(Fr) == kFrBytes && sizeof(G1Aff) == kAffBytes && sizeof(G1Xyzz) == kXyzzBytes &&
+                  sizeof(uint4) == 16,
+              "msm_plan.hpp's element sizes");
+static_assert(ev_slot::kCount <= Workspace::kEvents, "msm_plan.hpp's event slots");
+
 static thread_local sv_msm_stats g_last_stats;
 
 int msm_last_stats(sv_msm_stats* out) {
   *out = g_last_stats;
   return SV_OK;
-}
-
-static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
-
-// Sorted entries per accumulate thread for `entries` entries over nbt buckets (SVGPU_ACC_K forces it)
-static uint32_t plan_K(uint64_t entries, uint32_t nbt) {
-  uint64_t K = entries / (1u << 18);
-  if (K < 4) K = 4;
-  if (K > 32) K = 32;
-  // large n: buckets average entries / nbt > 32 entries; a chunk of about one average bucket keeps
-  // most crossing buckets at two pieces (joined inside k_accumulate), capped at 256 entries so the
-  // grid still has many rounds of waves (swept, tools/gpu_sweep_big.sh: 2^21 K = 64 4.47 -> 4.41 ms;
-  // 2^24 K = 256 32.0 ms, 512 32.4, 1024 33.4)
-  const uint64_t avg_bucket = entries / nbt;
-  if (K < avg_bucket) K = avg_bucket < 256 ? avg_bucket : 256;
-  if (const char* e = getenv("SVGPU_ACC_K")) K = (uint64_t)atoi(e);
-  if (K < 1) K = 1;
-  return (uint32_t)K;
-}
-
-// Host-fed pieces (a fraction of the points over the whole bucket set, so few entries per bucket):
-// chunks of about one average bucket, a multiple of 8, at least 16.  Round 3 (the 32-bit chain,
-// measured device-resident at the 2^20 plan's window) had found about two average buckets best while
-// that stayed <= 32 entries: a segment end then cost ~110 VALU instructions.  With the round-6
-// chain's raw-record segment ends, a quarter-size piece's accumulate at K = 32 filled only half the
-// chip's block slots; one average bucket (K = 24, 16, 16, 16 for the 2^20 pieces 5,4,4,3) measured
-// 2.538-2.570 ms per host-fed 2^20 MSM against 2.602-2.609 (SVGPU_ACC_K = 16 for every piece, two
-// passes, profiles/r06_host_piece_k.log).
-static uint32_t piece_K(uint64_t entries, uint32_t nbt) {
-  if (getenv("SVGPU_ACC_K")) return plan_K(entries, nbt);
-  const uint64_t avg = entries / nbt;
-  const uint64_t K = std::min<uint64_t>(std::max<uint64_t>((avg + 7) / 8 * 8, 16), 256);
-  return (uint32_t)K;
-}
-
-MsmPlan msm_plan(size_t n) {
-  MsmPlan p;
-  // GLV (k P = k1 P + k2 phi(P), 128-bit halves, split on the fly by the sort passes) halves the
-  // buckets, the bucket reduction and the host Horner for the same number of bucket entries, at the
-  // cost of a 32-B beta-x table per point.  Measured (r02, med ms, GLV off -> on): 2^14 0.79 -> 0.74,
-  // 2^16 0.98 -> 0.82, 2^18 1.75 -> 1.54, 2^20 2.11 -> 2.05, 2^21 3.74 -> 3.62; at 2^22 (6.88 ->
-  // 7.39) and 2^24 (27.3 -> 31.1) the larger gather working set (bases + beta-x beyond the 256 MiB
-  // Infinity Cache) slows the fill, so it is on up to 2^SVGPU_GLV_MAX_LOG points (default 21);
-  // SVGPU_GLV forces it.
-  int glv_max_log = 21;
-  if (const char* e = getenv("SVGPU_GLV_MAX_LOG")) glv_max_log = atoi(e);
-  p.glv = n >= (size_t(1) << 14) && n <= (size_t(1) << glv_max_log);
-  if (const char* e = getenv("SVGPU_GLV")) p.glv = atoi(e) != 0 && n >= 2;
-  p.npts = p.glv ? 2 * n : n;
-  // whole phi(P) records (one 64-B gather per k2 entry) while bases + table stay well inside the
-  // Infinity Cache; beta-x only above (measured at 2^20: 1.97-2.01 vs 2.01-2.15 ms, k_accumulate
-  // 1.39 vs 1.39-1.50 ms)
-  p.phi64 = n <= (size_t(1) << 20);
-  if (const char* e = getenv("SVGPU_GLV_PHI64")) p.phi64 = atoi(e) != 0;
-  const int nb = p.glv ? 128 : 255;
-  int lg = 0;
-  while ((size_t(1) << (lg + 1)) <= p.npts) lg++;
-  int c = lg - 4;
-  if (const char* e = getenv("SVGPU_WINDOW_BITS")) c = atoi(e);
-  if (c < 4) c = 4;
-  if (c > 16) c = 16;
-  p.c = c;
-  p.W = (nb + c - 1) / c;
-  p.B = 1u << (c - 1);
-  p.nbt = p.B * p.W;
-  uint64_t entries = (uint64_t)p.npts * p.W;
-  p.K = plan_K(entries, p.nbt);
-  p.T = cdiv(entries, p.K);
-  // reduction: J running-sum segments per window, NG subset groups of H = J/2 points
-  // 8 buckets per running-sum segment (swept: tools/gpu_sweep_red.sh); 4 with GLV, whose W / 2
-  // windows would otherwise leave half the SIMDs without a k_wsum wave
-  p.logL = p.glv ? 2 : 3;
-  if (const char* e = getenv("SVGPU_RED_LOG")) p.logL = atoi(e);
-  if (p.logL < 1) p.logL = 1;
-  if (p.logL > p.c - 3) p.logL = p.c - 3 > 1 ? p.c - 3 : 1;
-  // bucket reduction (SVGPU_GROUP_TREE): 1 (default) running sums + in-block subset-sum tree
-  // (k_wsum_tree<true>) when a window's segments fill whole 256-segment blocks, at most 64 of them;
-  // 2 the tree straight over the buckets (k_wsum_tree<false>, no running sums: L = 1); 0 k_wsum +
-  // k_group_sum(_q)
-  p.tree = 1;
-  if (const char* e = getenv("SVGPU_GROUP_TREE")) p.tree = atoi(e);
-  // k_accumulate's chain (AccChain): the 29-bit one unless SVGPU_ACC_R29=0; fixed per call, so
-  // the accumulate, fixup and reduction launches of one MSM agree on the stored form.  (A resident
-  // base set holds only the 29-bit table, so its calls use this chain whatever the switch says.)
-  p.r29 = !getenv("SVGPU_ACC_R29") || atoi(getenv("SVGPU_ACC_R29")) != 0;
-  if (p.tree == 2 && p.B % kTreeN == 0 && p.B / kTreeN <= 128) p.logL = 0;
-  else if (p.tree == 2) p.tree = 1;
-  p.J = p.B >> p.logL;
-  if (p.tree == 1 && !(p.J % kTreeN == 0 && p.J / kTreeN <= 64)) p.tree = 0;
-  p.logJ = 0;
-  while ((1u << p.logJ) < p.J) p.logJ++;
-  p.NG = 2 + p.logJ;
-  return p;
 }
 
 #define SV_LAUNCH_LOGB(KERNEL, LOGB, GRID, BLOCK, ...)                          \
@@ -1881,40 +1778,81 @@ struct SortOut {
   uint32_t K, T;     // entries per accumulate thread, accumulate threads
 };
 
+// One call: what every stage reads.  res (a resident base set, msm.hpp): the call's points are rows
+// [res->off, res->off + n) of the set.  Nothing is converted, checked or tabulated per call: the
+// sorts run on the scalars alone and emit the set's record indices (P at off + i, phi(P) at
+// N + off + i), the accumulate reads the set's table, a host-fed call stages scalars only, and
+// bases is not used.
+struct MsmCall {
+  Workspace* ws;
+  int device;
+  size_t n;
+  int mont_in;
+  const MsmFeed* feed;
+  const MsmResident* res;
+  MsmTuning t;
+  MsmPlan p;
+  MsmShape s;
+  bool lean, detail;  // MsmTuning::msm_lean, msm_stats (lean wins)
+  // a resident set's record indices: P_i of the call at r_off + i, phi(P_i) at r_phi + i
+  uint32_t r_off, r_phi;
+  const uint4* r_tab;
+  // inputs (device pointers; host-fed: the staging buffer) and the workspace's buffers (MsmBuffers)
+  const G1Aff* bases;
+  const Fr* scalars;
+  G1Aff* bases_m;
+  uint4 *phix, *stored;
+  G1Xyzz *ping, *bsum, *racc, *rtot, *gpart, *tree_out;
+  uint32_t *gst_all, *ent_all, *tst_all;
+  MsmScratch w;
+  std::vector<SortOut> so;                            // per piece
+  const uint32_t* half_gst[2] = {nullptr, nullptr};  // split: each window half's bucket starts
+
+  hipEvent_t ev(int slot) const { return ws->ev[slot]; }
+  hipEvent_t ev_if(bool on, int slot) const { return on ? ws->ev[slot] : nullptr; }
+};
+
 // Digits + two-level counting sort of points [0, m) (virtual points p_off + i and, with GLV,
 // nsplit + i: nsplit = m and p_off = 0 for a table of these m points, a resident set's phi record
-// base and offset otherwise) into so, on stream st.  With phix set (bases resident) k_bin_hist also writes the GLV table;
-// check_bases: Montgomery bases checked to be reduced on the way.
-static int msm_sort(const MsmPlan& p, const MsmScratch& w, const SortOut& so, const G1Aff* bases,
-                    const Fr* scalars, size_t m, int mont_in, int device, hipStream_t st, uint4* phix,
-                    uint32_t nsplit, int check_bases, hipEvent_t ev_sort_mid, hipStream_t side = nullptr,
-                    hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr, uint32_t w0 = 0,
-                    uint32_t nw = 0, uint4* stored = nullptr, uint32_t p_off = 0) {
+// base and offset otherwise) into so, on stream st.  With phix set (bases resident) k_bin_hist also
+// writes the GLV table; check_bases: Montgomery bases checked to be reduced on the way.
+struct SortArgs {
+  const G1Aff* bases = nullptr;
+  const Fr* scalars = nullptr;
+  size_t m = 0;  // real points (GLV: 2 m virtual ones)
+  uint4* phix = nullptr;
+  uint32_t nsplit = ~0u, p_off = 0;
+  int check_bases = 0;
+  uint32_t w0 = 0, nw = 0;  // windows [w0, w0 + nw) (nw = 0: all); so's buckets are those windows' (w - w0) * B + b
+  uint4* stored = nullptr;  // the histogram pass's digits source for the scatter (MsmTuning::sort_halves)
+  hipStream_t st = nullptr;
+  hipStream_t side = nullptr;  // MsmTuning::sort_fork: the large fine-sort regions' stream
+  hipEvent_t ev_mid = nullptr, ev_fork = nullptr, ev_join = nullptr;
+};
+static int msm_sort(const MsmCall& c, const SortOut& so, const SortArgs& a) {
+  const MsmPlan& p = c.p;
+  const MsmTuning& t = c.t;
+  const MsmScratch& w = c.w;
+  hipStream_t st = a.st;
   const int LOGB = p.c - 1;
   const int nb = p.glv ? 128 : 255;
   const uint32_t CB = (uint32_t)coarse_bits(p.c, nb), FB = (uint32_t)LOGB - CB, NBIN = 1u << CB;
-  if (nw == 0) nw = p.W;  // windows [w0, w0 + nw); so's buckets are those windows' (w - w0) * B + b
+  const uint32_t w0 = a.w0, nw = a.nw ? a.nw : p.W;
   const uint32_t nwb = nw * NBIN;
-  const uint32_t npts = (uint32_t)m;  // real points (GLV: 2 m virtual ones)
+  const uint32_t npts = (uint32_t)a.m;
   const uint32_t ep = p.glv ? 2 * p.W : p.W;
   const uint32_t nblk = cdiv(npts, sort_chunk((int)ep));
   // u32 entries when every virtual point index (below nsplit + m with GLV, p_off + m without) fits
-  const uint64_t vmax = p.glv ? (uint64_t)nsplit + npts : (uint64_t)p_off + npts;
-  int e32 = vmax <= (uint64_t(1) << (31 - FB)) ? 1 : 0;
-  if (const char* e = getenv("SVGPU_SORT_E32")) e32 = e32 && atoi(e) != 0;
-  static const int xcd = !getenv("SVGPU_SORT_XCD") || atoi(getenv("SVGPU_SORT_XCD")) != 0 ? 1 : 0;
-  // block-major per-block counts + the tiled scan (SVGPU_SORT_BM=0: key-major, k_bin_scan_chunks)
-  static const int bm = !getenv("SVGPU_SORT_BM") || atoi(getenv("SVGPU_SORT_BM")) != 0 ? 1 : 0;
-  // SVGPU_HIST_PF=0 (read per call): the histogram pass without the one-ahead loads (29-bit table path)
-  const int hist_pf = !getenv("SVGPU_HIST_PF") || atoi(getenv("SVGPU_HIST_PF")) != 0;
-  SV_LAUNCH_C(k_bin_hist, p.glv, p.c, dim3(nblk), dim3(kBlock), scalars, npts, mont_in, nblk, w.bcnt, w.err, bases,
-              phix, p.r29 ? kPhiVtab : p.phi64, check_bases, xcd, bm, w0, nw, stored, hist_pf);
+  const uint64_t vmax = p.glv ? (uint64_t)a.nsplit + npts : (uint64_t)a.p_off + npts;
+  const int e32 = vmax <= (uint64_t(1) << (31 - FB)) && t.sort_e32 ? 1 : 0;
+  const int xcd = t.sort_xcd, bm = t.sort_bm, hist_pf = t.hist_pf;
+  const int mont_in = c.mont_in;
+  SV_LAUNCH_C(k_bin_hist, p.glv, p.c, dim3(nblk), dim3(kBlock), a.scalars, npts, mont_in, nblk, w.bcnt, w.err,
+              a.bases, a.phix, p.r29 ? kPhiVtab : p.phi64, a.check_bases, xcd, bm, w0, nw, a.stored, hist_pf);
   SV_HIP(hipGetLastError());
-  if (ev_sort_mid) SV_HIP(hipEventRecord(ev_sort_mid, st));
+  if (a.ev_mid) SV_HIP(hipEventRecord(a.ev_mid, st));
   if (bm) {
-    // SVGPU_SCAN_KEYS=16: tiles of 16 keys (twice the blocks, 64 row groups per key); default 32
-    const char* ke = getenv("SVGPU_SCAN_KEYS");
-    if (ke && atoi(ke) == 16)
+    if (t.scan_keys == 16)
       hipLaunchKernelGGL(k_bin_scan_tiles<16>, dim3(cdiv(nwb, 16)), dim3(1024), 0, st, w.bcnt, nblk, nwb, w.btot);
     else
       hipLaunchKernelGGL(k_bin_scan_tiles<32>, dim3(cdiv(nwb, 32)), dim3(1024), 0, st, w.bcnt, nblk, nwb, w.btot);
@@ -1924,22 +1862,19 @@ static int msm_sort(const MsmPlan& p, const MsmScratch& w, const SortOut& so, co
   // (fusing this scan into k_bin_scan_chunks' last block -- device-scope fence + counter -- was
   // measured 12 -> 122 us for that kernel: the fence writes back the XCD's L2)
   hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, st, w.btot, nwb, w.bstart, so.gst + (size_t)nw * p.B);
-  SV_LAUNCH_C(k_bin_scatter, p.glv, p.c, dim3(nblk), dim3(kBlock), scalars, npts, mont_in, nblk, w.bcnt, w.btot, w.bstart,
-              w.tmp, e32, xcd, bm, w0, nw, stored, p_off, p.glv ? nsplit : 0u);
+  SV_LAUNCH_C(k_bin_scatter, p.glv, p.c, dim3(nblk), dim3(kBlock), a.scalars, npts, mont_in, nblk, w.bcnt, w.btot,
+              w.bstart, w.tmp, e32, xcd, bm, w0, nw, a.stored, a.p_off, p.glv ? a.nsplit : 0u);
   static thread_local int fine_attr_dev = -1;  // the > 64 KiB dynamic-LDS opt-in, once per thread/device
-  if (fine_attr_dev != device) {
+  if (fine_attr_dev != c.device) {
     SV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fine_sort<0>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFineLds));
     SV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fine_sort<1>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFineLds));
     SV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fine_sort<2>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFineLds));
-    fine_attr_dev = device;
+    fine_attr_dev = c.device;
   }
-  // one launch for both region kinds (SVGPU_FINE_SPLIT=1: the round-2 pair of launches, the large
-  // regions optionally on a side stream)
-  const bool fine_split = getenv("SVGPU_FINE_SPLIT") && atoi(getenv("SVGPU_FINE_SPLIT")) != 0;  // per call
-  if (!fine_split && !side) {
+  if (!t.fine_split && !a.side) {  // one launch for both region kinds
     hipLaunchKernelGGL(k_fine_sort<2>, dim3(nwb), dim3(1024), kFineLds, st, w.tmp, e32, w.bstart, FB, so.K, so.gst,
                        so.tstart, so.ent);
     SV_HIP(hipGetLastError());
@@ -1947,18 +1882,18 @@ static int msm_sort(const MsmPlan& p, const MsmScratch& w, const SortOut& so, co
   }
   // the two instantiations touch disjoint regions: with a side stream the large-region one (a few
   // dozen blocks, the top windows' crowded bins) runs concurrently with the other
-  hipStream_t big_st = side ? side : st;
-  if (side) {
-    SV_HIP(hipEventRecord(ev_fork, st));
-    SV_HIP(hipStreamWaitEvent(side, ev_fork, 0));
+  hipStream_t big_st = a.side ? a.side : st;
+  if (a.side) {
+    SV_HIP(hipEventRecord(a.ev_fork, st));
+    SV_HIP(hipStreamWaitEvent(a.side, a.ev_fork, 0));
   }
   hipLaunchKernelGGL(k_fine_sort<1>, dim3(nwb), dim3(1024), kFineLds, big_st, w.tmp, e32, w.bstart, FB, so.K,
                      so.gst, so.tstart, so.ent);
   hipLaunchKernelGGL(k_fine_sort<0>, dim3(nwb), dim3(1024), kFineLds, st, w.tmp, e32, w.bstart, FB, so.K, so.gst,
                      so.tstart, so.ent);
-  if (side) {
-    SV_HIP(hipEventRecord(ev_join, side));
-    SV_HIP(hipStreamWaitEvent(st, ev_join, 0));
+  if (a.side) {
+    SV_HIP(hipEventRecord(a.ev_join, a.side));
+    SV_HIP(hipStreamWaitEvent(st, a.ev_join, 0));
   }
   SV_HIP(hipGetLastError());
   return SV_OK;
@@ -1967,89 +1902,498 @@ static int msm_sort(const MsmPlan& p, const MsmScratch& w, const SortOut& so, co
 // Bucket accumulation of a sorted piece + its crossing-bucket fixups into bsum, on stream st
 // (add_into: the piece's bucket sums are added to what bsum holds -- k_accumulate<true> starts each
 // bucket's owner segment from it; otherwise complete buckets are stored and empty ones left alone).
-static int msm_acc(const MsmPlan& p, const MsmScratch& w, const SortOut& so, const G1Aff* bases, int add_into,
-                   hipStream_t st, G1Xyzz* bsum, const uint4* phix, uint32_t nsplit, hipEvent_t ev_acc_done,
-                   hipEvent_t ev_fix_mid, uint32_t nbt = 0) {
-  if (nbt == 0) nbt = p.nbt;  // the buckets so covers (a window half: its windows' buckets)
+struct AccArgs {
+  const G1Aff* bases = nullptr;
+  const uint4* phix = nullptr;
+  uint32_t nsplit = ~0u;
+  int add_into = 0;
+  G1Xyzz* bsum = nullptr;
+  uint32_t nbt = 0;  // the buckets so covers (0: all; a window half: its windows' buckets)
+  hipStream_t st = nullptr;
+  hipEvent_t ev_acc_done = nullptr, ev_fix_mid = nullptr;
+};
+static int msm_acc(const MsmCall& c, const MsmScratch& w, const SortOut& so, const AccArgs& a) {
+  const MsmPlan& p = c.p;
+  hipStream_t st = a.st;
+  const uint32_t nbt = a.nbt ? a.nbt : p.nbt;
   // (a point prefetch one entry ahead, k_accumulate<., ., 2>, measured no gain on the device path or
   // on the host-fed pieces' ~2 waves per SIMD: 2^20 host-fed 2.69-2.71 ms either way)
   const int r29 = p.r29;
-  if (r29) nsplit = ~0u;  // phix is the 29-bit chain's table of every virtual point (vtab_put): record idx
-  auto kern = add_into ? (r29 ? k_accumulate<true, true> : k_accumulate<true, false>)
-                       : (r29 ? k_accumulate<false, true> : k_accumulate<false, false>);
-  hipLaunchKernelGGL(kern, dim3(cdiv(so.T, kBlock)), dim3(kBlock), 0, st, bases, so.ent, so.gst, so.tstart, nbt,
-                     so.K, so.T, bsum, w.pfirst, w.plast, w.multi, w.nmulti, w.heavy, w.nheavy, phix, nsplit,
+  // with the 29-bit chain phix is its table of every virtual point (vtab_put): record idx
+  const uint32_t nsplit = r29 ? ~0u : a.nsplit;
+  auto kern = a.add_into ? (r29 ? k_accumulate<true, true> : k_accumulate<true, false>)
+                         : (r29 ? k_accumulate<false, true> : k_accumulate<false, false>);
+  hipLaunchKernelGGL(kern, dim3(cdiv(so.T, kBlock)), dim3(kBlock), 0, st, a.bases, so.ent, so.gst, so.tstart, nbt,
+                     so.K, so.T, a.bsum, w.pfirst, w.plast, w.multi, w.nmulti, w.heavy, w.nheavy, a.phix, nsplit,
                      p.phi64);
   SV_HIP(hipGetLastError());
-  if (ev_acc_done) SV_HIP(hipEventRecord(ev_acc_done, st));
+  if (a.ev_acc_done) SV_HIP(hipEventRecord(a.ev_acc_done, st));
   const uint32_t gm = std::min<uint32_t>(cdiv(nbt, kBlock), 1024);
   hipLaunchKernelGGL(k_fixup, dim3(gm + 256), dim3(kBlock), 0, st, so.gst, so.K, w.pfirst, w.plast, w.multi,
-                     w.nmulti, w.heavy, w.nheavy, gm, bsum, r29);
+                     w.nmulti, w.heavy, w.nheavy, gm, a.bsum, r29);
   SV_HIP(hipGetLastError());
-  if (ev_fix_mid) SV_HIP(hipEventRecord(ev_fix_mid, st));
+  if (a.ev_fix_mid) SV_HIP(hipEventRecord(a.ev_fix_mid, st));
   return SV_OK;
 }
 
-// Host-fed piece boundaries: SVGPU_H2D_SPLIT = comma-separated weights, else `pieces` equal pieces
-// (SVGPU_H2D_PIECES), else the default schedule: 4 equal pieces from 2^18 points.  A piece's
-// accumulate runs once its bases have landed (96 B per point at ~52 GB/s), and once the first piece
-// is in, the compute stream is the bottleneck (a piece's accumulate + fixup outlasts the next
-// piece's transfer), so what counts is the total accumulate work -- smaller pieces are less efficient
-// -- against starting early and leaving little after the last byte.  Measured at 2^20 (3 boxes,
-// tools/host_api_bench.py): 4 equal pieces 2.73-2.92 ms, 2,2,3,3,3,3 2.74-3.06, 2,3,3,3,3,2
-// 2.74-3.09, 3 pieces 3.41-3.47, 6 3.17-4.20 (before per-piece K), 1 piece 3.76-3.95.
-static std::vector<size_t> piece_bounds(size_t n, int pieces, const std::vector<double>& dflt) {
-  std::vector<double> wts;
-  if (const char* e = getenv("SVGPU_H2D_SPLIT")) {
-    for (const char* q = e; *q;) {
-      char* end = nullptr;
-      const double v = strtod(q, &end);
-      if (end == q) break;
-      if (v > 0) wts.push_back(v);
-      q = *end == ',' ? end + 1 : end;
-      if (*end && *end != ',') break;
-    }
-  }
-  if (wts.empty()) {
-    if (pieces > 0) {
-      wts.assign(std::min(pieces, 16), 1.0);
-    } else if (n >= (size_t(1) << 18) && !dflt.empty()) {
-      wts = dflt;
-    } else if (n >= (size_t(1) << 18)) {
-      // decreasing: the copy (1.7 ns per point) outpaces the pieces' accumulates (~1.3 ns), so the
-      // last piece -- whose accumulate is the call's tail -- is the smallest (round 4, 2^20, three
-      // A/B pairs: 5,4,4,3 2.594-2.597 ms vs 4 equal 2.639-2.657; 5,4,4,2,1 2.669-2.670)
-      wts = {5, 4, 4, 3};
-    } else if (n >= (size_t(1) << 15)) {
-      wts = {1, 1};
-    } else {
-      wts = {1};
-    }
-  }
-  if (wts.size() > 16) wts.resize(16);
-  // pieces below 4096 points are not worth a launch sequence
-  while (wts.size() > 1 && n < wts.size() * 4096) wts.pop_back();
-  double tot = 0;
-  for (double v : wts) tot += v;
-  std::vector<size_t> b{0};
-  double cum = 0;
-  for (size_t k = 0; k + 1 < wts.size(); k++) {
-    cum += wts[k];
-    // boundaries on multiples of 1024 points: every piece's copies start 32-KiB aligned (5 equal
-    // pieces, boundaries 32-B aligned, measured 3.13-3.17 ms vs 2.73-2.76 for 4 and 6)
-    const size_t at = ((size_t)((double)n * cum / tot)) & ~size_t(1023);
-    b.push_back(std::max(b.back(), std::min(n, at)));
-  }
-  b.push_back(n);
-  b.erase(std::unique(b.begin(), b.end()), b.end());
-  if (b.size() < 2) b = {0, n};
-  return b;
+// the fixup queue counters of piece (or window half) k: err[1 + 2k], err[2 + 2k], zeroed with the
+// error flag, so no per-piece memset sits between the accumulates
+static MsmScratch scratch_of(const MsmCall& c, int k) {
+  MsmScratch wk = c.w;
+  wk.nheavy = c.w.err + 1 + 2 * k;
+  wk.nmulti = c.w.err + 2 + 2 * k;
+  return wk;
 }
 
-// res (a resident base set, msm.hpp): the call's points are rows [res->off, res->off + n) of the set.
-// Nothing is converted, checked or tabulated per call: the sorts run on the scalars alone and emit
-// the set's record indices (P at off + i, phi(P) at N + off + i), the accumulate reads the set's
-// table, a host-fed call stages scalars only, and d_bases is not used.
+// MSMs of at most kSmallMsmTerms terms (MsmTuning::small_msm): a fed call's inputs are staged whole
+static int run_small(Workspace* ws, const void* d_bases, const void* d_scalars, size_t n, int form, int device,
+                     const MsmFeed* feed, const MsmResident* res, host::Xyzz* out) {
+  hipStream_t st = ws->stream;
+  g_last_stats = sv_msm_stats{};
+  int bases_form = form;
+  if (res) {  // the set's Montgomery rows
+    d_bases = reinterpret_cast<const G1Aff*>(res->rows) + res->off;
+    bases_form = SV_MONTGOMERY;
+  }
+  if (feed) {
+    MsmLayout in;
+    const size_t so = in.put("scalars", n, sizeof(Fr)), bo = in.put("bases", res ? 0 : n, sizeof(G1Aff));
+    SV_TRY(ws->reserve_in(in.total));
+    SV_TRY(feed->stage_scalars(0, n, ws->inbuf + so, st, ws->ev[ev_slot::kSmallScalars]));
+    d_scalars = ws->inbuf + so;
+    if (!res) {
+      SV_TRY(feed->stage_bases(0, n, ws->inbuf + bo, st, ws->ev[ev_slot::kSmallBases]));
+      d_bases = ws->inbuf + bo;
+    }
+  }
+  return msm_batch_windows_host(d_bases, d_scalars, nullptr, 1, n, form, bases_form, device, st, out);
+}
+
+// Reserve the workspace and the staging buffer by the one layout and form every pointer from it
+template <class T>
+static T* buf_at(char* base, size_t off) {
+  return off == MsmLayout::kAbsent ? nullptr : reinterpret_cast<T*>(base + off);
+}
+static int lay_out(MsmCall& c, const MsmMode& mode, const void* d_bases, const void* d_scalars) {
+  Workspace* ws = c.ws;
+  const MsmShape& s = c.s;
+  const MsmBuffers b = msm_buffers(c.n, mode, c.p, s);
+  SV_TRY(ws->reserve(b.ws.total));
+  SV_TRY(ws->reserve_pinned(s.nfinal * sizeof(G1Xyzz) + 256));
+  if (c.feed) {
+    SV_TRY(ws->reserve_in(b.in.total));
+    SV_TRY(ws->ensure_copy_stream());
+    SV_TRY(ws->ensure_sort_stream());
+    d_bases = buf_at<void>(ws->inbuf, b.in_bases);
+    d_scalars = ws->inbuf + b.in_scalars;
+  }
+  c.bases = reinterpret_cast<const G1Aff*>(d_bases);
+  c.scalars = reinterpret_cast<const Fr*>(d_scalars);
+  char* base = ws->buf;
+  c.bases_m = buf_at<G1Aff>(base, b.bases_m);
+  c.phix = buf_at<uint4>(base, b.phix);
+  c.stored = buf_at<uint4>(base, b.stored);
+  c.ping = buf_at<G1Xyzz>(base, b.ping);
+  c.bsum = buf_at<G1Xyzz>(base, b.bsum);
+  c.racc = buf_at<G1Xyzz>(base, b.racc);
+  c.rtot = buf_at<G1Xyzz>(base, b.rtot);
+  c.gpart = buf_at<G1Xyzz>(base, b.gpart);
+  c.tree_out = buf_at<G1Xyzz>(base, b.tree_out);
+  c.gst_all = buf_at<uint32_t>(base, b.gst);
+  c.ent_all = buf_at<uint32_t>(base, b.ent);
+  c.tst_all = buf_at<uint32_t>(base, b.tstart);
+  MsmScratch& w = c.w;
+  w.err = buf_at<uint32_t>(base, b.err);
+  w.bcnt = buf_at<uint32_t>(base, b.bcnt);
+  w.btot = buf_at<uint32_t>(base, b.btot);
+  w.bstart = buf_at<uint32_t>(base, b.bstart);
+  w.tmp = buf_at<uint64_t>(base, b.tmp);
+  w.pfirst = buf_at<G1Xyzz>(base, b.pfirst);
+  w.plast = buf_at<G1Xyzz>(base, b.plast);
+  w.heavy = buf_at<uint32_t>(base, b.heavy);
+  w.multi = buf_at<uint32_t>(base, b.multi);
+  w.nheavy = w.err + 1;  // zeroed with the error flag
+  w.nmulti = w.err + 2;
+  c.so.resize(s.pieces);
+  uint64_t eo = 0, to = 0;
+  for (int k = 0; k < s.pieces; k++) {
+    c.so[k] = {c.ent_all + eo, c.gst_all + (size_t)k * (c.p.nbt + 1), c.tst_all + to, s.K[k], s.T[k]};
+    eo += (uint64_t)(s.pb[k + 1] - s.pb[k]) * s.ep;
+    to += (uint64_t)s.T[k] + 1;
+  }
+  return SV_OK;
+}
+
+// Device inputs: canonical bases into the workspace's Montgomery copy (checked on the way)
+static const G1Aff* device_bases(const MsmCall& c) {
+  if (!c.s.conv) return c.bases;
+  hipLaunchKernelGGL(k_to_mont_bases, dim3(cdiv(c.n, kBlock)), dim3(kBlock), 0, c.ws->stream, c.bases, c.bases_m,
+                     (uint32_t)c.n, c.w.err);
+  return c.bases_m;
+}
+
+// Device inputs, a resident set included: one sort, one accumulate, on the compute stream
+static int run_device(MsmCall& c) {
+  namespace ev = ev_slot;
+  const MsmPlan& p = c.p;
+  Workspace* ws = c.ws;
+  hipStream_t st = ws->stream;
+  const bool res = c.res != nullptr;
+  const G1Aff* bases = res ? nullptr : device_bases(c);
+  hipStream_t side = nullptr;
+  if (!res && c.t.sort_fork) {
+    SV_TRY(ws->ensure_copy_stream());  // idle on the device path
+    side = ws->copy_stream;
+  }
+  const uint32_t nsplit = p.glv ? (res ? c.r_phi : (uint32_t)c.n) : ~0u;
+  SV_TRY(msm_sort(c, c.so[0], {.bases = bases, .scalars = c.scalars, .m = c.n, .phix = res ? nullptr : c.phix,
+                               .nsplit = nsplit, .p_off = c.r_off, .check_bases = res ? 0 : c.mont_in,
+                               .stored = c.stored, .st = st, .side = side, .ev_mid = c.ev_if(c.detail, ev::kSortMid),
+                               .ev_fork = c.ev(ev::kSortFork), .ev_join = c.ev(ev::kSortJoin)}));
+  SV_HIP(hipEventRecord(c.ev(ev::kAccBegin), st));
+  return msm_acc(c, c.w, c.so[0], {.bases = bases, .phix = res ? c.r_tab : c.phix, .nsplit = res ? ~0u : nsplit,
+                                   .bsum = c.bsum, .st = st, .ev_acc_done = c.ev(ev::kAccEnd),
+                                   .ev_fix_mid = c.ev_if(c.detail, ev::kFixEnd)});
+}
+
+// MsmTuning::msm_split: half A on the compute stream, half B on the sort stream beside A's accumulate
+static int run_device_split(MsmCall& c) {
+  namespace ev = ev_slot;
+  const MsmPlan& p = c.p;
+  const MsmShape& s = c.s;
+  Workspace* ws = c.ws;
+  hipStream_t st = ws->stream;
+  const G1Aff* bases = device_bases(c);
+  const uint32_t nsplit = p.glv ? (uint32_t)c.n : ~0u;
+  SV_TRY(ws->ensure_sort_stream());
+  hipStream_t ss = ws->sort_stream;
+  const uint32_t nbt_a = s.nwh[0] * p.B;  // half A's buckets
+  SortOut sh[2];
+  MsmScratch wh[2] = {scratch_of(c, 0), scratch_of(c, 1)};
+  for (int h = 0; h < 2; h++) {
+    sh[h].K = p.K;
+    sh[h].T = s.Th[h];
+    sh[h].ent = c.ent_all + (h ? (size_t)p.npts * s.nwh[0] : 0);  // at most npts entries per window
+    sh[h].gst = c.gst_all + (h ? (size_t)nbt_a + 1 : 0);
+    sh[h].tstart = c.tst_all + (h ? s.Th[0] + 1 : 0);
+    wh[h].pfirst = rec_at(c.w.pfirst, h ? s.Th[0] : 0, p.r29);
+    wh[h].plast = rec_at(c.w.plast, h ? s.Th[0] : 0, p.r29);
+    wh[h].heavy = c.w.heavy + (h ? nbt_a : 0);
+    wh[h].multi = c.w.multi + (h ? nbt_a : 0);
+    c.half_gst[h] = sh[h].gst;
+  }
+  G1Xyzz* bsum_b = rec_at(c.bsum, (size_t)nbt_a, p.r29);
+  // half A: sort (with the GLV table and the base check), accumulate
+  SV_TRY(msm_sort(c, sh[0], {.bases = bases, .scalars = c.scalars, .m = c.n, .phix = c.phix, .nsplit = nsplit,
+                             .check_bases = c.mont_in, .w0 = 0, .nw = s.nwh[0], .st = st,
+                             .ev_mid = c.ev_if(c.detail, ev::kSortMid)}));
+  SV_HIP(hipEventRecord(c.ev(ev::kAccBegin), st));
+  SV_HIP(hipStreamWaitEvent(ss, c.ev(ev::kAccBegin), 0));  // the sort scratch is free, the GLV table written
+  SV_TRY(msm_acc(c, wh[0], sh[0], {.bases = bases, .phix = c.phix, .nsplit = nsplit, .bsum = c.bsum, .nbt = nbt_a,
+                                   .st = st, .ev_acc_done = c.ev(ev::kAccEnd),
+                                   .ev_fix_mid = c.ev_if(c.detail, ev::kFixEnd)}));
+  // half B
+  SV_TRY(msm_sort(c, sh[1], {.bases = bases, .scalars = c.scalars, .m = c.n, .nsplit = nsplit, .w0 = s.nwh[0],
+                             .nw = s.nwh[1], .st = ss}));
+  SV_HIP(hipEventRecord(c.ev(ev::kHalfBAccBegin), ss));
+  SV_TRY(msm_acc(c, wh[1], sh[1], {.bases = bases, .phix = c.phix, .nsplit = nsplit, .bsum = bsum_b,
+                                   .nbt = s.nwh[1] * p.B, .st = ss, .ev_acc_done = c.ev(ev::kHalfBAccEnd)}));
+  SV_HIP(hipEventRecord(c.ev(ev::kHalfBEnd), ss));
+  return SV_OK;
+}
+
+// The host-fed call's feeder.  The workspace's helper thread stages the pieces back to back (a
+// pageable copy blocks the thread that issues it: queueing each piece's ~12 launches from that same
+// thread left the copy engine idle ~30 us per burst, rocprof trace); the calling thread queues a
+// piece's sort / accumulate as soon as the feeder has recorded the piece's events.  staged = stages
+// done (2k + 1: piece k's scalars, 2k + 2: its bases), -1 once the feeder failed.
+// Piece 0's scalars are staged by the CALLING thread, right after the helper is woken: the helper's
+// wake-up (a condition variable, tens of us) then overlaps that first copy instead of delaying it,
+// and the helper takes over from piece 0's bases (it spins until the scalars are issued, so the
+// copy stream keeps the scalars-then-bases order).
+class Feeder {
+ public:
+  explicit Feeder(const MsmCall& c) : c_(c) {}
+  ~Feeder() {  // on every exit: stop the helper after its current stage, then wait for it
+    if (!started_) return;
+    stop_.store(1);
+    c_.ws->wait_helper();
+  }
+  static int scalars_of(int k) { return 2 * k + 1; }
+  static int bases_of(int k) { return 2 * k + 2; }
+
+  int start() {
+    SV_TRY(c_.ws->run_helper([this] { feed_pieces(); }));
+    started_ = true;
+    // an exception leaving stage_scalars (host-pool allocation) unwinds through the destructor, whose
+    // stop releases the helper's wait; SV_GUARD then turns it into the call's error code
+    const std::vector<size_t>& pb = c_.s.pb;
+    const int rc0 = c_.feed->stage_scalars(pb[0], pb[1], const_cast<Fr*>(c_.scalars) + pb[0], c_.ws->copy_stream,
+                                           c_.ev(ev_slot::piece_scalars(0)));
+    if (rc0 != SV_OK) {
+      fail(rc0);  // the helper, spinning on staged, exits
+      return rc0;
+    }
+    staged_.store(scalars_of(0), std::memory_order_release);
+    return SV_OK;
+  }
+  // block until `stage` (scalars_of / bases_of a piece) has been issued; the feeder's error if it failed
+  int wait(int stage) {
+    int x;
+    while ((x = staged_.load(std::memory_order_acquire)) >= 0 && x < stage) std::this_thread::yield();
+    if (x < 0) {
+      set_error("%s", err_.c_str());
+      return rc_;
+    }
+    return SV_OK;
+  }
+
+ private:
+  void fail(int rc) {
+    rc_ = rc;
+    err_ = sv::last_error();
+    staged_.store(-1, std::memory_order_release);
+  }
+  void feed_pieces() {  // on the helper thread
+    const MsmFeed* feed = c_.feed;
+    const std::vector<size_t>& pb = c_.s.pb;
+    hipStream_t cs = c_.ws->copy_stream;
+    int rc = SV_OK;
+    // the helper thread has no SV_GUARD: an exception here (std::function / vector allocation in
+    // the host pool) becomes the call's SV_ERR_DEVICE instead of std::terminate
+    try {
+      int st0;
+      // also leave when the caller stops before staging piece 0 (its copy failed or threw)
+      while ((st0 = staged_.load(std::memory_order_acquire)) == 0 && !stop_.load(std::memory_order_relaxed))
+        std::this_thread::yield();
+      for (int k = 0; st0 > 0 && k < c_.s.pieces && !stop_.load(std::memory_order_relaxed); k++) {
+        const size_t lo = pb[k], hi = pb[k + 1];
+        if (k > 0) {
+          rc = feed->stage_scalars(lo, hi, const_cast<Fr*>(c_.scalars) + lo, cs, c_.ev(ev_slot::piece_scalars(k)));
+          if (rc != SV_OK) break;
+          staged_.store(scalars_of(k), std::memory_order_release);
+        }
+        if (!c_.res)
+          rc = feed->stage_bases(lo, hi, const_cast<G1Aff*>(c_.bases) + lo, cs, c_.ev(ev_slot::piece_bases(k)));
+        if (rc != SV_OK) break;
+        staged_.store(bases_of(k), std::memory_order_release);
+      }
+    } catch (const std::exception& e) {
+      set_error("host-fed MSM feeder: %s", e.what());
+      rc = SV_ERR_DEVICE;
+    } catch (...) {
+      set_error("host-fed MSM feeder: unknown exception");
+      rc = SV_ERR_DEVICE;
+    }
+    if (rc != SV_OK) fail(rc);
+  }
+
+  const MsmCall& c_;
+  std::atomic<int> staged_{0}, stop_{0};
+  int rc_ = SV_OK;
+  std::string err_;
+  bool started_ = false;
+};
+
+// Piece k's landed bases (points [lo, lo + m)) made ready for its accumulate: conversion / check and
+// the piece's table, on the sort stream behind the piece's sort (MsmTuning::fed_prep) or on the
+// compute stream; `sorted` is recorded on the sort stream behind whatever ran there.  Returns the
+// bases the accumulate reads.
+static int prepare_piece(const MsmCall& c, Feeder& feeder, int k, uint4* phix_k, const G1Aff** pbases) {
+  const MsmPlan& p = c.p;
+  const size_t lo = c.s.pb[k], m = c.s.pb[k + 1] - lo;
+  hipStream_t st = c.ws->stream, ss = c.ws->sort_stream;
+  hipEvent_t sorted = c.ev(ev_slot::piece_sorted(k));
+  const bool conv = c.s.conv;
+  G1Aff* db = const_cast<G1Aff*>(c.bases) + lo;
+  if (!c.t.fed_prep) SV_HIP(hipEventRecord(sorted, ss));
+  SV_TRY(feeder.wait(Feeder::bases_of(k)));
+  hipStream_t ps = c.t.fed_prep ? ss : st;
+  SV_HIP(hipStreamWaitEvent(ps, c.ev(ev_slot::piece_bases(k)), 0));
+  *pbases = conv ? c.bases_m + lo : db;
+  if (conv)  // canonical bases converted (and checked) once they have landed
+    hipLaunchKernelGGL(k_to_mont_bases, dim3(cdiv(m, kBlock)), dim3(kBlock), 0, ps, db, c.bases_m + lo, (uint32_t)m,
+                       c.w.err);
+  if (p.r29)  // the piece's table (29-bit chain) from the landed (converted) bases, checked
+    hipLaunchKernelGGL(k_vtab, dim3(cdiv(m, kBlock)), dim3(kBlock), 0, ps, *pbases, (uint32_t)m, phix_k,
+                       p.glv ? 1 : 0, conv ? nullptr : c.w.err);
+  else if (!p.glv)
+    hipLaunchKernelGGL(k_check_bases, dim3(cdiv(m, kBlock)), dim3(kBlock), 0, ps, db, (uint32_t)m, c.w.err);
+  if (!p.r29 && p.glv)  // the piece's phi table from the landed (converted) bases; Montgomery ones checked
+    hipLaunchKernelGGL(k_glv_phix, dim3(cdiv(m, kBlock)), dim3(kBlock), 0, ps, *pbases, (uint32_t)m, phix_k, p.phi64,
+                       conv ? nullptr : c.w.err);
+  SV_HIP(hipGetLastError());
+  if (c.t.fed_prep) SV_HIP(hipEventRecord(sorted, ss));
+  return SV_OK;
+}
+
+// Host-fed.  Piece k: the copy stream stages its scalars, then its bases; the sort stream sorts the
+// piece once its scalars have landed, beside the previous piece's accumulate, and prepares the
+// landed bases; the compute stream accumulates the piece into the one bucket set
+// (identity-initialised; pieces after the first add into it).  With a resident set there are no
+// bases to wait for: the piece's accumulate is gated on its sort alone and reads the set's table at
+// the piece's records.
+static int run_fed(MsmCall& c) {
+  namespace ev = ev_slot;
+  const MsmPlan& p = c.p;
+  const MsmShape& s = c.s;
+  Workspace* ws = c.ws;
+  hipStream_t st = ws->stream, cs = ws->copy_stream, ss = ws->sort_stream;
+  const bool res = c.res != nullptr;
+  if (s.pieces > 1) SV_HIP(hipMemsetAsync(c.bsum, 0, (size_t)p.nbt * s.rec_bytes, st));
+  SV_HIP(hipEventRecord(c.ev(ev::kFedFork), st));
+  SV_HIP(hipStreamWaitEvent(cs, c.ev(ev::kFedFork), 0));
+  SV_HIP(hipStreamWaitEvent(ss, c.ev(ev::kFedFork), 0));
+  Feeder feeder(c);
+  SV_TRY(feeder.start());
+  for (int k = 0; k < s.pieces; k++) {
+    const size_t lo = s.pb[k], m = s.pb[k + 1] - lo;
+    const uint32_t lo32 = (uint32_t)lo;
+    hipEvent_t sorted = c.ev(ev::piece_sorted(k));
+    // GLV: piece-local virtual points (i, m + i) over the piece's bases and its slice of the table;
+    // a resident set: its records
+    const uint32_t nsplit = p.glv ? (res ? c.r_phi + lo32 : (uint32_t)m) : ~0u;
+    uint4* phix_k = s.tab4 ? c.phix + s.tab4 * lo : nullptr;
+    SV_TRY(feeder.wait(Feeder::scalars_of(k)));
+    SV_HIP(hipStreamWaitEvent(ss, c.ev(ev::piece_scalars(k)), 0));
+    SV_TRY(msm_sort(c, c.so[k], {.scalars = c.scalars + lo, .m = m, .nsplit = nsplit,
+                                 .p_off = res ? c.r_off + lo32 : 0u, .st = ss}));
+    const G1Aff* pbases = nullptr;
+    if (res) SV_HIP(hipEventRecord(sorted, ss));
+    else SV_TRY(prepare_piece(c, feeder, k, phix_k, &pbases));
+    SV_HIP(hipStreamWaitEvent(st, sorted, 0));
+    if (k == 0) SV_HIP(hipEventRecord(c.ev(ev::kAccBegin), st));
+    SV_TRY(msm_acc(c, scratch_of(c, k), c.so[k],
+                   {.bases = pbases, .phix = res ? c.r_tab : phix_k, .nsplit = res ? ~0u : nsplit,
+                    .add_into = k > 0 ? 1 : 0, .bsum = c.bsum, .st = st,
+                    .ev_acc_done = c.ev_if(k == s.pieces - 1, ev::kAccEnd)}));
+  }
+  return SV_OK;
+}
+
+// Bucket reduction: running sums over segments of 2^logL buckets, then the subset sums (with
+// several host-fed pieces every bucket of bsum holds a value: no emptiness table).  (Reducing the top
+// windows first to overlap the host Horner with the lower ones was measured slower: each half-size
+// launch of these occupancy-bound kernels takes nearly as long as the whole -- reduce 0.40 -> 0.67 ms.)
+static int reduce_buckets(const MsmCall& c) {
+  const MsmPlan& p = c.p;
+  const MsmShape& s = c.s;
+  hipStream_t st = c.ws->stream;
+  const uint32_t* gst = s.pieces > 1 ? nullptr : c.so[0].gst;
+  if (p.tree == 0) {
+    hipLaunchKernelGGL(k_wsum, dim3(cdiv((uint64_t)p.J * p.W, kBlock)), dim3(kBlock), 0, st, c.bsum, gst, p.B, p.J,
+                       1u << p.logL, p.W, 1, c.racc, c.rtot, p.r29);
+    auto group_sum = c.t.group_quad ? k_group_sum_q : k_group_sum;
+    hipLaunchKernelGGL(group_sum, dim3(p.NG * p.W * s.gparts), dim3(kGroupBlock), 0, st, c.racc, c.rtot, p.J, p.logJ,
+                       s.gparts, c.ping, c.gpart, c.w.err + 64);
+    SV_HIP(hipGetLastError());
+    return SV_OK;
+  }
+  static thread_local int tree_attr_dev = -1;  // the > 64 KiB dynamic-LDS opt-in, once per thread/device
+  if (tree_attr_dev != c.device) {
+    SV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsum_tree<true, false>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * kTreeRow)));
+    SV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsum_tree<true, true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * kTreeRow)));
+    tree_attr_dev = c.device;
+  }
+  // windows [w0, w0 + nw) of the bucket sums xb (starts gs: empty buckets skipped) -> ping rows
+  // running sums on the 29-bit chain when the bucket sums are stored in its form
+  auto tree_run = p.r29 ? k_wsum_tree<true, true> : k_wsum_tree<true, false>;
+  auto reduce_windows = [&](const G1Xyzz* xb, const uint32_t* gs, uint32_t w0, uint32_t nw) {
+    if (p.tree == 2)
+      hipLaunchKernelGGL(k_wsum_tree<false>, dim3(p.J / kTreeN * nw), dim3(kTreeN), kTreeRow, st, xb, gs, p.B, p.J,
+                         1u, c.tree_out, p.r29);
+    else
+      hipLaunchKernelGGL(tree_run, dim3(p.J / kTreeN * nw), dim3(kTreeN), 2 * kTreeRow, st, xb, gs, p.B, p.J,
+                         1u << p.logL, c.tree_out, p.r29);
+    hipLaunchKernelGGL(k_group_fin, dim3(nw * p.NG), dim3(128), 0, st, c.tree_out, p.J / kTreeN, p.NG,
+                       p.tree == 2 ? 1u : 0u, c.ping + (size_t)w0 * p.NG);
+  };
+  if (s.split) {
+    reduce_windows(c.bsum, c.half_gst[0], 0, s.nwh[0]);  // beside half B's accumulate
+    SV_HIP(hipStreamWaitEvent(st, c.ev(ev_slot::kHalfBEnd), 0));
+    reduce_windows(rec_at(c.bsum, (size_t)s.nwh[0] * p.B, p.r29), c.half_gst[1], s.nwh[0], s.nwh[1]);
+  } else {
+    reduce_windows(c.bsum, gst, 0, p.W);
+  }
+  SV_HIP(hipGetLastError());
+  return SV_OK;
+}
+
+// a host-fed call that fails part-way leaves copies (and sorts) queued on its other streams: drain
+// them before the lease returns the staging buffers to the pool
+struct Drain {
+  Workspace* ws;
+  bool armed;
+  ~Drain() {
+    if (armed) (void)ws->quiesce();
+  }
+};
+
+// The group sums and the error word to the host, the host Horner, the call's stats
+static int finish(const MsmCall& c, Drain& drain, host::Xyzz* out) {
+  namespace ev = ev_slot;
+  const MsmPlan& p = c.p;
+  Workspace* ws = c.ws;
+  hipStream_t st = ws->stream;
+  const size_t nfinal = c.s.nfinal;
+  SV_HIP(hipMemcpyAsync(ws->pinned, c.ping, nfinal * sizeof(G1Xyzz) + 4, hipMemcpyDeviceToHost, st));
+  SV_HIP(hipStreamSynchronize(st));
+  drain.armed = false;  // the copy and sort streams' work all precedes the compute stream's end
+  uint32_t errv;
+  memcpy(&errv, ws->pinned + nfinal * sizeof(G1Xyzz), 4);
+  if (errv) {
+    set_error("invalid input: %s%s", (errv & 1) ? "base coordinate not reduced mod p; " : "",
+              (errv & 2) ? "scalar not reduced mod r" : "");
+    return SV_ERR_ARG;
+  }
+  auto t0 = std::chrono::steady_clock::now();
+  *out = host_combine(p, reinterpret_cast<const host::Xyzz*>(ws->pinned));
+  auto t1 = std::chrono::steady_clock::now();
+
+  sv_msm_stats& s = g_last_stats;
+  auto span = [&](int from, int to) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, c.ev(from), c.ev(to));
+    return ms;
+  };
+  if (c.detail && !c.feed) {
+    s.digits_ms = span(ev::kStart, ev::kSortMid);  // digits + coarse histogram (digits never stored; the GLV halves are)
+    s.sort_ms = span(ev::kSortMid, ev::kAccBegin);
+    s.fixup_ms = span(ev::kAccEnd, ev::kFixEnd);
+    s.reduce_ms = span(ev::kFixEnd, ev::kEnd);
+  } else if (c.lean) {
+    s.digits_ms = s.sort_ms = s.fixup_ms = s.reduce_ms = -1.0f;  // not measured
+  } else {  // digits folded into sort_ms, fixup into reduce_ms
+    s.digits_ms = 0;
+    s.sort_ms = span(ev::kStart, ev::kAccBegin);
+    s.fixup_ms = 0;
+    s.reduce_ms = span(ev::kAccEnd, ev::kEnd);
+  }
+  // host-fed: "accumulate" spans the first piece's accumulate to the last piece's (transfers included);
+  // split: the two halves' accumulate launches, each from its own start to its own end (they may
+  // overlap in time), and accumulate_span_ms from the first start to the last end
+  const float ms = span(ev::kAccBegin, ev::kAccEnd);
+  s.accumulate_ms = ms;
+  s.accumulate_span_ms = ms;
+  s.accumulate_launches = 1;
+  if (c.s.split) {
+    const float mb = span(ev::kHalfBAccBegin, ev::kHalfBAccEnd), mspan = span(ev::kAccBegin, ev::kHalfBAccEnd);
+    s.accumulate_ms = ms + mb;
+    s.accumulate_span_ms = std::max(ms, mspan);
+    s.accumulate_launches = 2;
+  }
+  s.host_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+  s.total_ms = c.lean ? -1.0f : span(ev::kStart, ev::kEnd) + s.host_ms;
+  s.window_bits = p.c;
+  s.num_windows = p.W;
+  s.accumulate_launch_units = cdiv((uint64_t)p.npts * p.W, p.K);
+  s.entries = (uint64_t)p.npts * p.W;
+  return SV_OK;
+}
+
+// Every single-MSM entry point: validate, the small route, plan, lay out, dispatch, reduce, finish
 static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, int form, int device,
                         hipStream_t user_stream, const MsmFeed* feed, host::Xyzz* out,
                         const MsmResident* res = nullptr) {
@@ -2067,502 +2411,38 @@ static int msm_run_impl(const void* d_bases, const void* d_scalars, size_t n, in
   }
   WsLease lease(device, user_stream);
   if (!lease.ok()) return SV_ERR_DEVICE;
-  Workspace* ws = lease.get();
-  hipStream_t st = ws->stream;
-  // Small MSMs (round 5): the window sums on the device, the window Horner on the host
-  // (msm_batch_windows_host, msm_batch.hip): the pipeline below is latency-bound there (a 64-term
-  // MSM took ~0.35 ms: a dozen launches, serial accumulate chunks, the reduction kernels and a host
-  // Horner over 52 windows).  SVGPU_SMALL_MSM=0 keeps the pipeline (read per call).
-  if (n <= kSmallMsmTerms && !(getenv("SVGPU_SMALL_MSM") && atoi(getenv("SVGPU_SMALL_MSM")) == 0)) {
-    g_last_stats = sv_msm_stats{};
-    if (res) {  // the set's Montgomery rows
-      const void* rows = reinterpret_cast<const G1Aff*>(res->rows) + res->off;
-      const void* ds = d_scalars;
-      if (feed) {
-        SV_TRY(ws->reserve_in(Workspace::aligned(n * sizeof(Fr))));
-        SV_TRY(feed->stage_scalars(0, n, ws->inbuf, st, ws->ev[0]));
-        ds = ws->inbuf;
-      }
-      return msm_batch_windows_host(rows, ds, nullptr, 1, n, form, SV_MONTGOMERY, device, st, out);
-    }
-    if (!feed) return msm_batch_windows_host(d_bases, d_scalars, nullptr, 1, n, form, form, device, st, out);
-    const size_t sbytes = Workspace::aligned(n * sizeof(Fr));
-    SV_TRY(ws->reserve_in(sbytes + n * sizeof(G1Aff)));
-    void* ds = ws->inbuf;
-    void* db = ws->inbuf + sbytes;
-    SV_TRY(feed->stage_scalars(0, n, ds, st, ws->ev[0]));
-    SV_TRY(feed->stage_bases(0, n, db, st, ws->ev[1]));
-    return msm_batch_windows_host(db, ds, nullptr, 1, n, form, form, device, st, out);
-  }
-  MsmPlan p = msm_plan(n);
-  if (res) p.r29 = 1;
-  // host-fed inputs arrive in pieces (piece_bounds): piece k is sorted on the sort stream once its
-  // scalars have landed and accumulated on the compute stream once its bases have, while later
-  // pieces are still in flight
-  const std::vector<size_t> pb = feed ? piece_bounds(n, feed->pieces, feed->split) : std::vector<size_t>{0, n};
-  const int pieces = (int)pb.size() - 1;
-  const uint32_t ep = p.glv ? 2 * p.W : p.W;  // entries per real point
-  size_t max_piece = 0;
-  uint64_t tst_total = 0;
-  uint32_t Tmax = 0;
-  std::vector<SortOut> so(pieces);
-  for (int k = 0; k < pieces; k++) {
-    const uint64_t e = (uint64_t)(pb[k + 1] - pb[k]) * ep;
-    max_piece = std::max(max_piece, pb[k + 1] - pb[k]);
-    so[k].K = feed ? piece_K(e, p.nbt) : p.K;  // each piece's chunk length for its own size
-    so[k].T = cdiv(e, so[k].K);
-    tst_total += (uint64_t)so[k].T + 1;
-    Tmax = std::max(Tmax, so[k].T);
-  }
-  const uint64_t entries = (uint64_t)n * ep;              // all pieces
-  const uint64_t piece_entries = (uint64_t)max_piece * ep;  // the sort scratch, reused per piece
-  // SVGPU_MSM_SPLIT=1 (device-resident inputs; off by default): the windows in two halves
-  // A = [0, WA), B = [WA, W), each sorted, accumulated and reduced on its own, so that half B's sort
-  // runs on the sort stream beside half A's accumulate and half A's reduction beside half B's
-  // accumulate.  Measured slower at 2^20 (round 4, two A/B pairs: 1.89-1.92 vs 1.81-1.82 ms/step):
-  // a half sort costs 0.155 ms, not half of 0.195 (every point's GLV split and digits are still
-  // computed), and the two accumulate launches barely overlap (span 1.47 ms, their own durations
-  // 1.52 ms): k_accumulate holds two 256-thread blocks per CU, so half A's 512 blocks already fill
-  // the chip and half B's wait for them -- one round of blocks each, as the whole launch's two.
-  const bool split_env = getenv("SVGPU_MSM_SPLIT") && atoi(getenv("SVGPU_MSM_SPLIT")) != 0;  // per call
-  const bool split = !feed && !res && split_env && p.W >= 2 && p.tree == 1 && n >= (size_t(1) << 16);
-  const uint32_t nwh[2] = {split ? p.W / 2 : p.W, split ? p.W - p.W / 2 : 0};
-  uint32_t Th[2] = {0, 0};
-  if (split) {
-    for (int h = 0; h < 2; h++) Th[h] = cdiv((uint64_t)p.npts * nwh[h], p.K);
-    tst_total = (uint64_t)Th[0] + 1 + Th[1] + 1;
-    Tmax = Th[0] + Th[1];
-  }
+  MsmCall c;
+  c.ws = lease.get();
+  c.t = msm_tuning();
+  if (n <= kSmallMsmTerms && c.t.small_msm) return run_small(c.ws, d_bases, d_scalars, n, form, device, feed, res, out);
+  c.device = device;
+  c.n = n;
+  c.mont_in = form == SV_MONTGOMERY ? 1 : 0;
+  c.feed = feed;
+  c.res = res;
+  c.p = msm_plan(n, c.t);
+  if (res) c.p.r29 = 1;
+  MsmMode mode;
+  mode.canonical = form == SV_CANONICAL;
+  mode.fed = feed != nullptr;
+  mode.resident = res != nullptr;
+  if (feed) mode.pieces = feed->pieces, mode.split = feed->split;
+  c.s = msm_shape(n, mode, c.p, c.t);
+  c.lean = c.t.msm_lean;
+  c.detail = c.t.msm_stats && !c.lean;
+  c.r_off = res ? (uint32_t)res->off : 0u;
+  c.r_phi = res ? (uint32_t)(res->N + res->off) : 0u;
+  c.r_tab = res ? reinterpret_cast<const uint4*>(res->vtab) : nullptr;
+  SV_TRY(lay_out(c, mode, d_bases, d_scalars));
 
-  // ---- workspace layout
-  const int nb = p.glv ? 128 : 255;
-  const uint32_t CB = (uint32_t)coarse_bits(p.c, nb), NBIN = 1u << CB;
-  const uint32_t nwb = p.W * NBIN;
-  const uint32_t nblk = cdiv(max_piece, sort_chunk((int)ep));
-  size_t bytes = 0;
-  auto add = [&](size_t b) { bytes += Workspace::aligned(b); };
-  const bool conv = (form == SV_CANONICAL) && !res;
-  if (conv) add(n * sizeof(G1Aff));
-  // GLV: beta x (or phi(P)) per point; the 29-bit chain: its table of every virtual point instead
-  // (none for a resident set: the accumulate reads the set's own table)
-  const size_t tab4 = res ? 0 : p.r29 ? vtab_uint4_per_point(p.glv) : (p.glv ? (p.phi64 ? 4 : 2) : 0);  // uint4 per point
-  if (tab4) add(n * tab4 * sizeof(uint4));
-  const size_t nfinal = (size_t)p.W * p.NG;
-  uint32_t gparts = nfinal < 256 ? 2 : 1;      // k_group_sum blocks per group (see there)
-  if (const char* e = getenv("SVGPU_GROUP_P")) gparts = (uint32_t)std::max(1, atoi(e));
-  if (gparts > p.J / 2) gparts = p.J / 2;
-  const size_t nerr = 64 + nfinal;             // err flag, heavy/multi queue counters, group counters
-  add(nerr * 4);
-  add((size_t)nwb * nblk * 4);                // bcnt
-  add((size_t)nwb * 4);                       // btot
-  add(((size_t)nwb + 1) * 4);                 // bstart
-  add(piece_entries * 8);                     // tmp (coarse-binned entries)
-  // the histogram pass's digits source for the scatter (32 B per point; the device path without
-  // window halves only; SVGPU_SORT_HALVES=0, read per call: recomputed by the scatter instead)
-  const char* sh_env = getenv("SVGPU_SORT_HALVES");
-  const bool keep_halves = !feed && !split && !(sh_env && atoi(sh_env) == 0);
-  if (keep_halves) add(n * 32);
-  add((((size_t)p.nbt + 1) * pieces + 1) * 4);  // gst per piece (+ 1: two window halves)
-  add(entries * 4);                           // ent (every piece's sorted entries)
-  add(tst_total * 4);                         // tstart per piece
-  const size_t rec_bytes = bucket_rec_bytes(p.r29);  // bucket-sum records (29-bit chain: 144 B)
-  add((size_t)Tmax * rec_bytes * 2);          // pfirst, plast
-  add((size_t)p.nbt * rec_bytes);             // bsum
-  add((size_t)p.nbt * 4);                     // heavy-bucket queue
-  add((size_t)p.nbt * 4);                     // multi-thread-bucket queue
-  add((size_t)p.J * p.W * sizeof(G1Xyzz) * 2);  // acc_j, T_j
-  add(nfinal * sizeof(G1Xyzz));                 // group sums
-  add(nfinal * gparts * sizeof(G1Xyzz));        // group slice sums
-  const bool group_tree = p.tree != 0;  // see msm_plan
-  const size_t ntree = group_tree ? (size_t)p.W * (p.J / kTreeN) * kTreeOut : 0;
-  add(ntree * sizeof(G1Xyzz));                  // per-block tree outputs
-  SV_TRY(ws->reserve(bytes));
-  SV_TRY(ws->reserve_pinned(nfinal * sizeof(G1Xyzz) + 256));
-  if (feed) {
-    const size_t bbytes = res ? 0 : Workspace::aligned(n * sizeof(G1Aff));
-    SV_TRY(ws->reserve_in(bbytes + Workspace::aligned(n * sizeof(Fr))));
-    SV_TRY(ws->ensure_copy_stream());
-    SV_TRY(ws->ensure_sort_stream());
-    d_bases = res ? nullptr : ws->inbuf;
-    d_scalars = ws->inbuf + bbytes;
-  }
-  // a resident set's record indices: P_i of the call at r_off + i, phi(P_i) at r_phi + i
-  const uint32_t r_off = res ? (uint32_t)res->off : 0u, r_phi = res ? (uint32_t)(res->N + res->off) : 0u;
-  const uint4* r_tab = res ? reinterpret_cast<const uint4*>(res->vtab) : nullptr;
-
-  const G1Aff* bases = reinterpret_cast<const G1Aff*>(d_bases);
-  const Fr* scalars = reinterpret_cast<const Fr*>(d_scalars);
-  const int mont_in = form == SV_MONTGOMERY ? 1 : 0;
-  G1Aff* bases_m = conv ? ws->carve<G1Aff>(n) : nullptr;
-  uint4* phix = tab4 ? ws->carve<uint4>(tab4 * n) : nullptr;
-  MsmScratch w;
-  // the group sums and the error flag / counters share one region: one D2H copy reads both
-  G1Xyzz* ping = ws->carve<G1Xyzz>(nfinal + (nerr * 4 + sizeof(G1Xyzz) - 1) / sizeof(G1Xyzz));
-  w.err = reinterpret_cast<uint32_t*>(ping + nfinal);
-  w.bcnt = ws->carve<uint32_t>((size_t)nwb * nblk);
-  w.btot = ws->carve<uint32_t>(nwb);
-  w.bstart = ws->carve<uint32_t>((size_t)nwb + 1);
-  w.tmp = ws->carve<uint64_t>(piece_entries);
-  uint4* stored = keep_halves ? ws->carve<uint4>(2 * n) : nullptr;
-  uint32_t* gst_all = ws->carve<uint32_t>(((size_t)p.nbt + 1) * pieces + 1);
-  uint32_t* ent_all = ws->carve<uint32_t>(entries);
-  uint32_t* tst_all = ws->carve<uint32_t>(tst_total);
-  w.pfirst = reinterpret_cast<G1Xyzz*>(ws->carve<uint4>(Tmax * rec_bytes / 16));
-  w.plast = reinterpret_cast<G1Xyzz*>(ws->carve<uint4>(Tmax * rec_bytes / 16));
-  G1Xyzz* bsum = reinterpret_cast<G1Xyzz*>(ws->carve<uint4>(p.nbt * rec_bytes / 16));
-  w.heavy = ws->carve<uint32_t>(p.nbt);
-  w.multi = ws->carve<uint32_t>(p.nbt);
-  w.nheavy = w.err + 1;  // zeroed with the error flag
-  w.nmulti = w.err + 2;
-  G1Xyzz* racc = ws->carve<G1Xyzz>((size_t)p.J * p.W);
-  G1Xyzz* rtot = ws->carve<G1Xyzz>((size_t)p.J * p.W);
-  G1Xyzz* gpart = ws->carve<G1Xyzz>(nfinal * gparts);
-  G1Xyzz* tree_out = group_tree ? ws->carve<G1Xyzz>(ntree) : nullptr;
-  {
-    uint64_t eo = 0, to = 0;
-    for (int k = 0; k < pieces; k++) {
-      so[k].ent = ent_all + eo;
-      so[k].gst = gst_all + (size_t)k * (p.nbt + 1);
-      so[k].tstart = tst_all + to;
-      eo += (uint64_t)(pb[k + 1] - pb[k]) * ep;
-      to += (uint64_t)so[k].T + 1;
-    }
-  }
-
-  hipEvent_t* ev = ws->ev;
-  // each event record between kernels costs ~5.5 us of idle GPU (rocprof trace): the accumulate is
-  // always bracketed (bench.py's live roofline), the sort / fixup splits only with SVGPU_MSM_STATS=1
-  // SVGPU_MSM_LEAN=1 (read per call): only the accumulate's two events, no sort / reduce split
-  static const bool detail_env = getenv("SVGPU_MSM_STATS") && atoi(getenv("SVGPU_MSM_STATS")) != 0;
-  const char* lean_env = getenv("SVGPU_MSM_LEAN");
-  const bool lean = lean_env && atoi(lean_env) != 0;
-  const bool detail = detail_env && !lean;
-  const char* fork_env = getenv("SVGPU_SORT_FORK");
-  const bool fork_sort = fork_env && atoi(fork_env) != 0;  // off: measured slower (the join delays the accumulate)
-  // a host-fed call that fails part-way leaves copies (and sorts) queued on its other streams: drain
-  // them before the lease returns the staging buffers to the pool
-  struct Drain {
-    Workspace* ws;
-    bool armed;
-    ~Drain() {
-      if (armed) (void)ws->quiesce();
-    }
-  } drain{ws, feed != nullptr || split};
-  if (!lean) SV_HIP(hipEventRecord(ev[0], st));
-  SV_HIP(hipMemsetAsync(w.err, 0, nerr * 4, st));
-  const uint32_t* half_gst[2] = {nullptr, nullptr};  // split: each window half's bucket starts
-  if (!feed && res) {
-    SV_TRY(msm_sort(p, w, so[0], nullptr, scalars, n, mont_in, device, st, nullptr, p.glv ? r_phi : ~0u, 0,
-                    detail ? ev[1] : nullptr, nullptr, nullptr, nullptr, 0, 0, stored, r_off));
-    SV_HIP(hipEventRecord(ev[2], st));
-    SV_TRY(msm_acc(p, w, so[0], nullptr, 0, st, bsum, r_tab, ~0u, ev[3], detail ? ev[4] : nullptr));
-  } else if (!feed) {
-    if (conv) {
-      hipLaunchKernelGGL(k_to_mont_bases, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, st, bases, bases_m, (uint32_t)n,
-                         w.err);
-      bases = bases_m;
-    }
-    hipStream_t side = nullptr;
-    if (fork_sort) {
-      SV_TRY(ws->ensure_copy_stream());  // idle on the device path
-      side = ws->copy_stream;
-    }
-    const uint32_t nsplit = p.glv ? (uint32_t)n : ~0u;
-    if (split) {
-      SV_TRY(ws->ensure_sort_stream());
-      hipStream_t ss = ws->sort_stream;
-      SortOut sh[2];
-      MsmScratch wh[2] = {w, w};
-      for (int h = 0; h < 2; h++) {
-        sh[h].K = p.K;
-        sh[h].T = Th[h];
-        sh[h].ent = ent_all + (h ? (size_t)p.npts * nwh[0] : 0);  // at most npts entries per window
-        sh[h].gst = gst_all + (h ? (size_t)nwh[0] * p.B + 1 : 0);
-        sh[h].tstart = tst_all + (h ? Th[0] + 1 : 0);
-        wh[h].pfirst = rec_at(w.pfirst, h ? Th[0] : 0, p.r29);
-        wh[h].plast = rec_at(w.plast, h ? Th[0] : 0, p.r29);
-        wh[h].heavy = w.heavy + (h ? nwh[0] * p.B : 0);
-        wh[h].multi = w.multi + (h ? nwh[0] * p.B : 0);
-        wh[h].nheavy = w.err + 1 + 2 * h;
-        wh[h].nmulti = w.err + 2 + 2 * h;
-      }
-      // half A on the compute stream: sort (with the GLV table and the base check), accumulate
-      SV_TRY(msm_sort(p, w, sh[0], bases, scalars, n, mont_in, device, st, phix, nsplit, mont_in,
-                      detail ? ev[1] : nullptr, nullptr, nullptr, nullptr, 0, nwh[0]));
-      SV_HIP(hipEventRecord(ev[2], st));
-      SV_HIP(hipStreamWaitEvent(ss, ev[2], 0));  // the sort scratch is free, the GLV table written
-      SV_TRY(msm_acc(p, wh[0], sh[0], bases, 0, st, bsum, phix, nsplit, ev[3], detail ? ev[4] : nullptr,
-                     nwh[0] * p.B));
-      // half B on the sort stream, beside A's accumulate
-      SV_TRY(msm_sort(p, w, sh[1], bases, scalars, n, mont_in, device, ss, nullptr, nsplit, 0, nullptr, nullptr,
-                      nullptr, nullptr, nwh[0], nwh[1]));
-      SV_HIP(hipEventRecord(ev[62], ss));
-      SV_TRY(msm_acc(p, wh[1], sh[1], bases, 0, ss, rec_at(bsum, (size_t)nwh[0] * p.B, p.r29), phix, nsplit, ev[63], nullptr,
-                     nwh[1] * p.B));
-      SV_HIP(hipEventRecord(ev[8], ss));
-      half_gst[0] = sh[0].gst;
-      half_gst[1] = sh[1].gst;
-    } else {
-      SV_TRY(msm_sort(p, w, so[0], bases, scalars, n, mont_in, device, st, phix, nsplit, mont_in,
-                      detail ? ev[1] : nullptr, side, ev[60], ev[61], 0, 0, stored));
-      SV_HIP(hipEventRecord(ev[2], st));
-      SV_TRY(msm_acc(p, w, so[0], bases, 0, st, bsum, phix, nsplit, ev[3], detail ? ev[4] : nullptr));
-    }
-  } else {
-    // Piece k: the copy stream stages its scalars, then its bases (the pageable copy blocks this
-    // thread, so the piece's sort is queued in between and runs during the base transfer); the sort
-    // stream sorts the piece once its scalars have landed, beside the previous piece's accumulate;
-    // the compute stream converts / checks the landed bases, writes the piece's GLV table and
-    // accumulates the piece into the one bucket set (identity-initialised; pieces after the first
-    // add into it).
-    hipStream_t cs = ws->copy_stream, ss = ws->sort_stream;
-    const bool prep_on_sort = !getenv("SVGPU_FED_PREP") || atoi(getenv("SVGPU_FED_PREP")) != 0;
-    if (pieces > 1) SV_HIP(hipMemsetAsync(bsum, 0, (size_t)p.nbt * rec_bytes, st));
-    SV_HIP(hipEventRecord(ev[6], st));
-    SV_HIP(hipStreamWaitEvent(cs, ev[6], 0));
-    SV_HIP(hipStreamWaitEvent(ss, ev[6], 0));
-    // A feeder (the workspace's helper thread) stages the pieces back to back (a pageable copy blocks
-    // the thread that issues it: queueing each piece's ~12 launches from that same thread left the
-    // copy engine idle ~30 us per burst, rocprof trace); this thread queues a piece's sort /
-    // accumulate as soon as the feeder has recorded the piece's events.  staged = stages done (2k + 1: piece k's scalars, 2k + 2: its
-    // bases), -1 once the feeder failed.
-    // Piece 0's scalars are staged by THIS thread, right after the helper is woken: the helper's
-    // wake-up (a condition variable, tens of us) then overlaps that first copy instead of delaying
-    // it, and the helper takes over from piece 0's bases (it spins until the scalars are issued, so
-    // the copy stream keeps the scalars-then-bases order).
-    std::atomic<int> staged{0}, stop{0};
-    int feed_rc = SV_OK;
-    std::string feed_err;
-    SV_TRY(ws->run_helper([&] {
-      int rc = SV_OK;
-      // the helper thread has no SV_GUARD: an exception here (std::function / vector allocation in
-      // the host pool) becomes the call's SV_ERR_DEVICE instead of std::terminate
-      try {
-        int st0;
-        // also leave when the caller stops before staging piece 0 (its copy failed or threw)
-        while ((st0 = staged.load(std::memory_order_acquire)) == 0 && !stop.load(std::memory_order_relaxed))
-          std::this_thread::yield();
-        for (int k = 0; st0 > 0 && k < pieces && !stop.load(std::memory_order_relaxed); k++) {
-          const size_t lo = pb[k], hi = pb[k + 1];
-          if (k > 0) {
-            rc = feed->stage_scalars(lo, hi, const_cast<Fr*>(scalars) + lo, cs, ev[8 + 3 * k]);
-            if (rc != SV_OK) break;
-            staged.store(2 * k + 1, std::memory_order_release);
-          }
-          if (!res) rc = feed->stage_bases(lo, hi, const_cast<G1Aff*>(bases) + lo, cs, ev[9 + 3 * k]);
-          if (rc != SV_OK) break;
-          staged.store(2 * k + 2, std::memory_order_release);
-        }
-      } catch (const std::exception& e) {
-        set_error("host-fed MSM feeder: %s", e.what());
-        rc = SV_ERR_DEVICE;
-      } catch (...) {
-        set_error("host-fed MSM feeder: unknown exception");
-        rc = SV_ERR_DEVICE;
-      }
-      if (rc != SV_OK) {
-        feed_rc = rc;
-        feed_err = sv::last_error();
-        staged.store(-1, std::memory_order_release);
-      }
-    }));
-    struct Join {  // on every exit: stop the feeder after its current stage, then wait for it
-      Workspace* ws;
-      std::atomic<int>& stop;
-      ~Join() {
-        stop.store(1);
-        ws->wait_helper();
-      }
-    } join{ws, stop};
-    {
-      // an exception leaving stage_scalars (host-pool allocation) unwinds through join, whose stop
-      // releases the helper's wait above; SV_GUARD then turns it into the call's error code
-      const int rc0 = feed->stage_scalars(pb[0], pb[1], const_cast<Fr*>(scalars) + pb[0], cs, ev[8]);
-      if (rc0 != SV_OK) {
-        feed_rc = rc0;
-        feed_err = sv::last_error();
-        staged.store(-1, std::memory_order_release);  // the helper, spinning on it, exits
-        return rc0;
-      }
-      staged.store(1, std::memory_order_release);
-    }
-    auto wait_stage = [&](int v) -> int {
-      int x;
-      while ((x = staged.load(std::memory_order_acquire)) >= 0 && x < v) std::this_thread::yield();
-      if (x < 0) {
-        set_error("%s", feed_err.c_str());
-        return feed_rc;
-      }
-      return SV_OK;
-    };
-    for (int k = 0; k < pieces; k++) {
-      const size_t lo = pb[k], hi = pb[k + 1], m = hi - lo;
-      hipEvent_t sc_ready = ev[8 + 3 * k], b_ready = ev[9 + 3 * k], sorted = ev[10 + 3 * k];
-      G1Aff* db = const_cast<G1Aff*>(bases) + lo;
-      Fr* dsc = const_cast<Fr*>(scalars) + lo;
-      // GLV: piece-local virtual points (i, m + i) over the piece's bases and its slice of the table
-      const uint32_t nsplit = p.glv ? (uint32_t)m : ~0u;
-      uint4* phix_k = tab4 ? phix + tab4 * lo : nullptr;
-      SV_TRY(wait_stage(2 * k + 1));
-      SV_HIP(hipStreamWaitEvent(ss, sc_ready, 0));
-      if (res) {
-        // a resident set: no bases to wait for, the piece's accumulate is gated on its sort alone and
-        // reads the set's table at the piece's records
-        const uint32_t lo32 = (uint32_t)lo;
-        SV_TRY(msm_sort(p, w, so[k], nullptr, dsc, m, mont_in, device, ss, nullptr, p.glv ? r_phi + lo32 : ~0u, 0,
-                        nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, r_off + lo32));
-        SV_HIP(hipEventRecord(sorted, ss));
-        SV_HIP(hipStreamWaitEvent(st, sorted, 0));
-        if (k == 0) SV_HIP(hipEventRecord(ev[2], st));
-        MsmScratch wk = w;
-        wk.nheavy = w.err + 1 + 2 * k;
-        wk.nmulti = w.err + 2 + 2 * k;
-        SV_TRY(msm_acc(p, wk, so[k], nullptr, k > 0 ? 1 : 0, st, bsum, r_tab, ~0u,
-                       k == pieces - 1 ? ev[3] : nullptr, nullptr));
-        continue;
-      }
-      SV_TRY(msm_sort(p, w, so[k], nullptr, dsc, m, mont_in, device, ss, nullptr, nsplit, 0, nullptr));
-      if (!prep_on_sort) SV_HIP(hipEventRecord(sorted, ss));
-      SV_TRY(wait_stage(2 * k + 2));
-      // the landed bases' preparation (conversion / check / the piece's phi table) runs on the sort
-      // stream behind the piece's sort (round 3: off the compute stream, whose back-to-back
-      // accumulates are the host-fed path's critical path once the first piece has landed);
-      // SVGPU_FED_PREP=0 keeps it on the compute stream
-      hipStream_t ps = prep_on_sort ? ss : st;
-      SV_HIP(hipStreamWaitEvent(ps, b_ready, 0));
-      const G1Aff* pbases = conv ? bases_m + lo : db;
-      if (conv)  // canonical bases converted (and checked) once they have landed
-        hipLaunchKernelGGL(k_to_mont_bases, dim3(cdiv(m, kBlock)), dim3(kBlock), 0, ps, db, bases_m + lo,
-                           (uint32_t)m, w.err);
-      if (p.r29)  // the piece's table (29-bit chain) from the landed (converted) bases, checked
-        hipLaunchKernelGGL(k_vtab, dim3(cdiv(m, kBlock)), dim3(kBlock), 0, ps, pbases, (uint32_t)m, phix_k,
-                           p.glv ? 1 : 0, conv ? nullptr : w.err);
-      else if (!p.glv)
-        hipLaunchKernelGGL(k_check_bases, dim3(cdiv(m, kBlock)), dim3(kBlock), 0, ps, db, (uint32_t)m, w.err);
-      if (!p.r29 && p.glv)  // the piece's phi table from the landed (converted) bases; Montgomery ones checked
-        hipLaunchKernelGGL(k_glv_phix, dim3(cdiv(m, kBlock)), dim3(kBlock), 0, ps, pbases, (uint32_t)m, phix_k,
-                           p.phi64, conv ? nullptr : w.err);
-      SV_HIP(hipGetLastError());
-      if (prep_on_sort) SV_HIP(hipEventRecord(sorted, ss));
-      SV_HIP(hipStreamWaitEvent(st, sorted, 0));
-      if (k == 0) SV_HIP(hipEventRecord(ev[2], st));
-      // each piece has its own fixup queue counters (err[1 + 2k], err[2 + 2k], zeroed with the
-      // error flag), so no per-piece memset sits between the accumulates
-      MsmScratch wk = w;
-      wk.nheavy = w.err + 1 + 2 * k;
-      wk.nmulti = w.err + 2 + 2 * k;
-      SV_TRY(msm_acc(p, wk, so[k], pbases, k > 0 ? 1 : 0, st, bsum, phix_k, nsplit,
-                     k == pieces - 1 ? ev[3] : nullptr, nullptr));
-    }
-  }
-  // bucket reduction: running sums over segments of 2^logL buckets, then the subset sums (with
-  // several host-fed pieces every bucket of bsum holds a value: no emptiness table).  (Reducing the top windows
-  // first to overlap the host Horner with the lower ones was measured slower: each half-size launch
-  // of these occupancy-bound kernels takes nearly as long as the whole -- reduce 0.40 -> 0.67 ms.)
-  const bool group_quad = !getenv("SVGPU_GROUP_QUAD") || atoi(getenv("SVGPU_GROUP_QUAD")) != 0;
-  if (group_tree) {
-    static thread_local int tree_attr_dev = -1;  // the > 64 KiB dynamic-LDS opt-in, once per thread/device
-    if (tree_attr_dev != device) {
-      SV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsum_tree<true, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * kTreeRow)));
-      SV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wsum_tree<true, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * kTreeRow)));
-      tree_attr_dev = device;
-    }
-    // windows [w0, w0 + nw) of the bucket sums xb (starts gs: empty buckets skipped) -> ping rows
-    // running sums on the 29-bit chain when the bucket sums are stored in its form
-    auto tree_run = p.r29 ? k_wsum_tree<true, true> : k_wsum_tree<true, false>;
-    auto reduce_windows = [&](const G1Xyzz* xb, const uint32_t* gs, uint32_t w0, uint32_t nw) {
-      if (p.tree == 2)
-        hipLaunchKernelGGL(k_wsum_tree<false>, dim3(p.J / kTreeN * nw), dim3(kTreeN), kTreeRow, st, xb, gs, p.B,
-                           p.J, 1u, tree_out, p.r29);
-      else
-        hipLaunchKernelGGL(tree_run, dim3(p.J / kTreeN * nw), dim3(kTreeN), 2 * kTreeRow, st, xb, gs,
-                           p.B, p.J, 1u << p.logL, tree_out, p.r29);
-      hipLaunchKernelGGL(k_group_fin, dim3(nw * p.NG), dim3(128), 0, st, tree_out, p.J / kTreeN, p.NG,
-                         p.tree == 2 ? 1u : 0u, ping + (size_t)w0 * p.NG);
-    };
-    if (split) {
-      reduce_windows(bsum, half_gst[0], 0, nwh[0]);  // beside half B's accumulate
-      SV_HIP(hipStreamWaitEvent(st, ev[8], 0));
-      reduce_windows(rec_at(bsum, (size_t)nwh[0] * p.B, p.r29), half_gst[1], nwh[0], nwh[1]);
-    } else {
-      reduce_windows(bsum, pieces > 1 ? nullptr : so[0].gst, 0, p.W);
-    }
-  } else {
-    hipLaunchKernelGGL(k_wsum, dim3(cdiv((uint64_t)p.J * p.W, kBlock)), dim3(kBlock), 0, st, bsum,
-                       pieces > 1 ? nullptr : so[0].gst, p.B, p.J, 1u << p.logL, p.W, 1, racc, rtot, p.r29);
-    if (group_quad)
-      hipLaunchKernelGGL(k_group_sum_q, dim3(p.NG * p.W * gparts), dim3(kGroupBlock), 0, st, racc, rtot, p.J,
-                         p.logJ, gparts, ping, gpart, w.err + 64);
-    else
-      hipLaunchKernelGGL(k_group_sum, dim3(p.NG * p.W * gparts), dim3(kGroupBlock), 0, st, racc, rtot, p.J,
-                         p.logJ, gparts, ping, gpart, w.err + 64);
-  }
-  SV_HIP(hipGetLastError());
-  if (!lean) SV_HIP(hipEventRecord(ev[5], st));
-  SV_HIP(hipMemcpyAsync(ws->pinned, ping, nfinal * sizeof(G1Xyzz) + 4, hipMemcpyDeviceToHost, st));
-  SV_HIP(hipStreamSynchronize(st));
-  drain.armed = false;  // the copy and sort streams' work all precedes the compute stream's end
-  uint32_t errv;
-  memcpy(&errv, ws->pinned + nfinal * sizeof(G1Xyzz), 4);
-  if (errv) {
-    set_error("invalid input: %s%s", (errv & 1) ? "base coordinate not reduced mod p; " : "",
-              (errv & 2) ? "scalar not reduced mod r" : "");
-    return SV_ERR_ARG;
-  }
-  auto t0 = std::chrono::steady_clock::now();
-  *out = host_combine(p, reinterpret_cast<const host::Xyzz*>(ws->pinned));
-  auto t1 = std::chrono::steady_clock::now();
-
-  sv_msm_stats& s = g_last_stats;
-  float ms = 0;
-  if (detail && !feed) {
-    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-    s.digits_ms = ms;  // digits + coarse histogram (digits never stored; the GLV halves are)
-    (void)hipEventElapsedTime(&ms, ev[1], ev[2]);
-    s.sort_ms = ms;
-    (void)hipEventElapsedTime(&ms, ev[3], ev[4]);
-    s.fixup_ms = ms;
-    (void)hipEventElapsedTime(&ms, ev[4], ev[5]);
-    s.reduce_ms = ms;
-  } else if (lean) {
-    s.digits_ms = s.sort_ms = s.fixup_ms = s.reduce_ms = -1.0f;  // not measured
-  } else {  // digits folded into sort_ms, fixup into reduce_ms
-    s.digits_ms = 0;
-    (void)hipEventElapsedTime(&ms, ev[0], ev[2]);
-    s.sort_ms = ms;
-    s.fixup_ms = 0;
-    (void)hipEventElapsedTime(&ms, ev[3], ev[5]);
-    s.reduce_ms = ms;
-  }
-  // host-fed: "accumulate" spans the first piece's accumulate to the last piece's (transfers included);
-  // split: the two halves' accumulate launches, each from its own start to its own end (they may
-  // overlap in time), and accumulate_span_ms from the first start to the last end
-  (void)hipEventElapsedTime(&ms, ev[2], ev[3]);
-  s.accumulate_ms = ms;
-  s.accumulate_span_ms = ms;
-  s.accumulate_launches = 1;
-  if (split) {
-    float mb = 0, mspan = 0;
-    (void)hipEventElapsedTime(&mb, ev[62], ev[63]);
-    (void)hipEventElapsedTime(&mspan, ev[2], ev[63]);
-    s.accumulate_ms = ms + mb;
-    s.accumulate_span_ms = std::max(ms, mspan);
-    s.accumulate_launches = 2;
-  }
-  s.host_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-  if (lean) {
-    s.total_ms = -1.0f;
-  } else {
-    (void)hipEventElapsedTime(&ms, ev[0], ev[5]);
-    s.total_ms = ms + s.host_ms;
-  }
-  s.window_bits = p.c;
-  s.num_windows = p.W;
-  s.accumulate_launch_units = cdiv((uint64_t)p.npts * p.W, p.K);
-  s.entries = (uint64_t)p.npts * p.W;
-  return SV_OK;
+  hipStream_t st = c.ws->stream;
+  Drain drain{c.ws, feed != nullptr || c.s.split};
+  if (!c.lean) SV_HIP(hipEventRecord(c.ev(ev_slot::kStart), st));
+  SV_HIP(hipMemsetAsync(c.w.err, 0, c.s.nerr * 4, st));
+  SV_TRY(feed ? run_fed(c) : c.s.split ? run_device_split(c) : run_device(c));
+  SV_TRY(reduce_buckets(c));
+  if (!c.lean) SV_HIP(hipEventRecord(c.ev(ev_slot::kEnd), st));
+  return finish(c, drain, out);
 }
 
 int msm_run_device(const void* d_bases, const void* d_scalars, size_t n, int form, int device,
