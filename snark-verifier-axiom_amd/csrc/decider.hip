@@ -702,6 +702,9 @@ __device__ __forceinline__ Lz lz_mul9(const Lz& a) {  // (a << 3) + a
 // a mod p for a < 2^264, to [0, 2p): k = floor(a / p) from the top 40 bits (exact in double; never
 // above the true quotient, at most one below), a - k p.  Slots hold such partially reduced values:
 // the Montgomery product is exact for inputs below 2p (4 p^2 < 2^256 p) and returns them reduced.
+// (tests/test_gpu_decider_ops.py runs this on every multiple of p up to 2^264 - 1 and its
+// neighbours, next to every multiple of 2^256, and next to the multiples of 2^224 at which the
+// estimate steps -- a >> 224 = j (p_top + 1) -- with the low words all zeros and all ones)
 __device__ __forceinline__ Fq lz_reduce(const Lz& a) {
   const uint64_t hi = ((uint64_t)a.v[8] << 32) | a.v[7];  // a >> 224
   // times 1 / (p_top + 1) instead of a division: the product stays below a / p (the divisor's
@@ -731,7 +734,8 @@ __device__ __forceinline__ Fq fq_canon(const Fq& a) {
   return br ? a : d;
 }
 __device__ __forceinline__ Fq2 fq2_canon(const Fq2& a) { return {fq_canon(a.c0), fq_canon(a.c1)}; }
-// 2p - a for a in [0, 2p]: the negation of a partially reduced value
+// the negation of a partially reduced value, again in [0, 2p): 2p - a for a in (0, 2p], and 0 for
+// a raw 0 (2p - 0 would leave the slot range)
 __device__ __forceinline__ Fq fq_neg2p(const Fq& a) {
   static constexpr uint32_t P2[8] = {0xb0f9fa8eu, 0x7841182du, 0xd0e3951au, 0x2f02d522u,
                                      0x0302b0bbu, 0x70a08b6du, 0xc2634053u, 0x60c89ce5u};
@@ -739,7 +743,7 @@ __device__ __forceinline__ Fq fq_neg2p(const Fq& a) {
   uint32_t br = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) r.v[i] = __builtin_subc(P2[i], a.v[i], br, &br);
-  return r;
+  return a.is_zero() ? a : r;
 }
 template <int L>
 __device__ __forceinline__ Lz xmove(const Lz& a) {
@@ -797,9 +801,12 @@ __device__ __forceinline__ void place(const Lz& l, const Lz& nl, bool imag, bool
 // |m| sum to at most 102 (positive ones to 97, negative ones to 56, w_mul and w_sqr alike), and
 // 102 * 2^24 < 2^31, so every partial sum stays an int32 per limb and a level of the lane sum is
 // ONE v_add_u32 per limb with the partner's limb read through DPP: no carry chain, whose VCC
-// hazards cost an s_nop per dependent v_addc.  The coefficient sum lies in (-112 p, 194 p);
-// biased by 240 p it is positive and below 434 p < 2^263, and one signed carry pass normalises it
-// into the 9-word Lz form that lz_reduce takes.
+// hazards cost an s_nop per dependent v_addc.  The coefficient sum lies in (-112 p, 194 p); w_mul's
+// conj flags negate whole terms, which raises the negative figure to 59 (kConjA or kConjB) or 80
+// (both) with the positive one still within 97: (-160 p, 194 p).  Biased by 240 p the sum is
+// positive and below 434 p < 2^263, and one signed carry pass normalises it into the 9-word Lz
+// form that lz_reduce takes.  (tests/test_gpu_decider_ops.py restates the multiplier table and
+// confirms these figures.)
 constexpr int kL24 = 11;  // 11 x 24 = 264 bits
 struct Limbs24 {
   uint32_t v[kL24];
@@ -836,7 +843,8 @@ __device__ __forceinline__ void split24(const Fq& a, uint32_t l[kL24]) {
 }
 // biased signed-limb sum -> 9 words: carries t_i >> 24 (arithmetic); word j = bytes 4j .. 4j + 3
 // gathered from the low three bytes of two adjacent t (v_perm_b32); the top word takes all of t_10
-// above bit 16 (the biased sum is non-negative)
+// above bit 16 (the biased sum is non-negative).  Tested over the whole of (-112 p, 194 p): every
+// multiple of p and its neighbours, both ends, and limbs at +-102 (2^24 - 1) in runs and alternating
 __device__ __forceinline__ Lz norm24(const uint32_t s[kL24]) {
   uint32_t t[kL24];
   int32_t c = 0;
@@ -1021,7 +1029,8 @@ SV_WG_FN void w_frob(const WLane& L, Fq2* __restrict__ dst, const Fq2* a, int n,
   __syncthreads();
 }
 
-// dst = conj(a) (odd w-coefficients negated) or a copy
+// dst = conj(a) (odd w-coefficients negated) or a copy.  Slots are [0, 2p); both representatives
+// of a residue are valid inputs, and the result is a slot value again
 SV_WG_FN void w_conj(Fq2* __restrict__ dst, const Fq2* a, bool neg_odd = true) {
   const int t = threadIdx.x;
   if (t < 12) {
@@ -1035,7 +1044,9 @@ SV_WG_FN void w_conj(Fq2* __restrict__ dst, const Fq2* a, bool neg_odd = true) {
 }
 
 // ni = N^-1 for N = a conj(a) (even coefficients = an Fq6 element c0 + c1 v + c2 v^2, v = w^2), as
-// in g_inv: the three t_j on three lanes, the norm d and its Fq2 inverse (one fe_inv) on one lane
+// in g_inv: the three t_j on three lanes, the norm d and its Fq2 inverse (one fe_inv) on one lane.
+// Slots are [0, 2p); both representatives of a residue are valid inputs (canonicalised on entry),
+// the odd coefficients of nn are not read, and ni is fully reduced
 __device__ __forceinline__ void w_norm_inv(Fq2* __restrict__ ni, const Fq2* nn, Fq2* tj, Fq2* di) {
   const int t = threadIdx.x;
   if (t < 3) {
@@ -1406,6 +1417,7 @@ __global__ void __launch_bounds__(wg::kThreads) k_decide_wg(const G1Aff* __restr
   const Fq2* e = S + 6 * kResultSlot;
   if (t < 6) {
     if (t == 0) {  // conj(W) / W == 1  <=>  the odd w-coefficients of W are zero
+      // slots are [0, 2p): a zero coefficient is a raw 0 or a raw p, hence the fq2_canon
       const bool ok = fq2_canon(e[1]).is_zero() && fq2_canon(e[3]).is_zero() && fq2_canon(e[5]).is_zero();
       verdict[acc] = ok ? 1 : 0;
     }
