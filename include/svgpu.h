@@ -248,7 +248,8 @@ int sv_bn254_g1_msm_bases_device(uint64_t handle, size_t offset, const sv_fe* d_
  * SV_ERR_ARG ("not reduced") for that call, found on the device; the handle stays usable.  Calls
  * are re-entrant on one handle like the other resident calls.
  * Not covered: host coefficients fed in pieces, high end first, so that the copy overlaps the scan
- * and the sort; several polynomials or several points per call; multi-device sets.              */
+ * and the sort; multi-device sets.  Several polynomials at one point: the batched opening below;
+ * several points: one batched opening per point (svgpu.kzg.gwc19_open groups the queries).      */
 int sv_bn254_fr_poly_div_linear_device(const sv_fe* d_coeffs, size_t n, const sv_fe* z, int form,
                                        int device, void* stream, sv_fe* d_quotient,
                                        sv_fe* out_eval) SV_NOEXCEPT;
@@ -257,6 +258,45 @@ int sv_bn254_kzg_open(uint64_t handle, size_t offset, const sv_fe* coeffs, size_
 int sv_bn254_kzg_open_device(uint64_t handle, size_t offset, const sv_fe* d_coeffs, size_t n,
                              const sv_fe* z, int form, void* stream, sv_fe* out_eval,
                              sv_g1_jacobian* out_witness_partial) SV_NOEXCEPT;
+
+/* ---- batched KZG opening on a resident base set: one GWC19 point set per call -----------
+ * GWC19 (snark-verifier/src/pcs/kzg/multiopen/gwc19.rs:43-80) groups its queries by point and
+ * takes ONE witness per point set: for the m polynomials p_j opened at z and a challenge v,
+ *   c = sum_j v^j p_j (v^0 = 1),  e_j = p_j(z),  q = (c - c(z)) / (X - z),
+ *   witness = sum_{k<N-1} q_k set[offset + k],  N = max lens[j]
+ * (a shorter polynomial is zero past its end).  One pass over the polynomials gives c and every
+ * e_j (each polynomial is read once; csrc/kzg_open.hip), the division above runs over c, and ONE
+ * MSM of the set gives the witness, where m single openings run m.  All mod r and a group sum:
+ * every output is determined bit for bit.
+ * d_polys and lens are HOST arrays of m device pointers and lengths; each polynomial lives on
+ * the set's device (or on `device`), 16-byte aligned, in `form`; a pointer may appear more than
+ * once; inputs are only read.  `form` covers the coefficients, z, v, the evaluations (out_evals:
+ * m host elements) and d_combined; the Jacobian partial is canonical.  `stream` may be NULL.
+ * fr_poly_combine_eval_device: c and the e_j alone.  d_combined (N elements in HBM; may be NULL =
+ *   evaluate only) must not overlap a polynomial ("overlaps", SV_ERR_ARG).
+ * kzg_open_batch_device: the opening.  c and q live in pooled scratch in Montgomery form beside
+ *   the per-call table (pointers, lengths, powers of v: one small copy on the call's stream).
+ *   N == 1 runs no MSM and gives the identity, as does an all-zero quotient (v = 0 with a constant
+ *   p_0, or c == 0); sv_msm_last_stats reflects the witness MSM.
+ * Checked before any device work, in this order: bad form, a null pointer (d_polys, lens, z, v,
+ * out_evals, the witness pointer, any d_polys[j]) or a misaligned d_polys[j] SV_ERR_ARG; m == 0 or
+ * any lens[j] == 0 SV_ERR_EMPTY; m > SV_OPEN_BATCH_MAX or any lens[j] > 2^26 SV_ERR_LEN (of a
+ * longer batch only the first SV_OPEN_BATCH_MAX entries are looked at); z not below r, then v
+ * SV_ERR_ARG ("not reduced"); combine_eval: d_combined misaligned or overlapping a polynomial
+ * SV_ERR_ARG; opening: unknown or destroyed handle, then offset + (N - 1) beyond the set
+ * SV_ERR_ARG.  A coefficient not below r is SV_ERR_ARG ("not reduced") for that call, found on the
+ * device; the handle stays usable and nothing is retained.  Calls are re-entrant on one handle.
+ * The pass keeps m * ceil(N / 1024) block totals (32 B each) in scratch: 2 MiB at m = 64, N = 2^20.
+ * Not covered: a batch fed from host coefficients (a caller with host coefficients uploads them
+ * first); the SHPLONK (bdfg21) prover; multi-device sets.                                       */
+#define SV_OPEN_BATCH_MAX 4096 /* polynomials per call */
+int sv_bn254_fr_poly_combine_eval_device(const sv_fe* const* d_polys, const uint64_t* lens, size_t m,
+                                         const sv_fe* z, const sv_fe* v, int form, int device,
+                                         void* stream, sv_fe* d_combined, sv_fe* out_evals) SV_NOEXCEPT;
+int sv_bn254_kzg_open_batch_device(uint64_t handle, size_t offset, const sv_fe* const* d_polys,
+                                   const uint64_t* lens, size_t m, const sv_fe* z, const sv_fe* v,
+                                   int form, void* stream, sv_fe* out_evals,
+                                   sv_g1_jacobian* out_witness_partial) SV_NOEXCEPT;
 
 /* ---- Poseidon sponge over BN254 Fr --------------------------
  * x^5 HADES permutation, width t = 3 (R_F 8, R_P 57, rate 2: the SDK's PoseidonTranscript,

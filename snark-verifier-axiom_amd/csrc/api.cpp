@@ -1225,6 +1225,172 @@ int sv_bn254_kzg_open_device(uint64_t handle, size_t offset, const sv_fe* d_coef
   SV_GUARD_END
 }
 
+// ---- several polynomials at one point (GWC19's point sets): one pass, one division, one witness MSM ----
+namespace {
+// the batch's checks up to v, in order: form / null / alignment, empty, length, z, v (no device
+// touched).  Only the first SV_OPEN_BATCH_MAX entries of the arrays are looked at: a longer batch is
+// refused by its m.  *N = the longest length.
+int batch_call_args(const sv_fe* const* d_polys, const uint64_t* lens, size_t m, const sv_fe* z, const sv_fe* v,
+                    int form, const void* out_evals, const void* out, size_t* N) {
+  SV_TRY(check_form(form));
+  if (!d_polys || !lens || !z || !v || !out_evals || !out) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  const size_t seen = std::min<size_t>(m, SV_OPEN_BATCH_MAX);
+  for (size_t j = 0; j < seen; j++) {
+    if (!d_polys[j]) {
+      sv::set_error("null pointer (polynomial %zu)", j);
+      return SV_ERR_ARG;
+    }
+    if ((uintptr_t)d_polys[j] % 16) {
+      sv::set_error("polynomial %zu is not 16-byte aligned", j);
+      return SV_ERR_ARG;
+    }
+  }
+  if (m == 0) {
+    sv::set_error("batch should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  for (size_t j = 0; j < seen; j++)
+    if (lens[j] == 0) {
+      sv::set_error("polynomial should not be empty (polynomial %zu)", j);
+      return SV_ERR_EMPTY;
+    }
+  if (m > SV_OPEN_BATCH_MAX) {
+    sv::set_error("m = %zu exceeds the per-call limit of %d polynomials", m, SV_OPEN_BATCH_MAX);
+    return SV_ERR_LEN;
+  }
+  size_t longest = 0;
+  for (size_t j = 0; j < m; j++) {
+    if (lens[j] > kMaxSetRows) {
+      sv::set_error("n = %llu exceeds the per-device limit 2^26 (polynomial %zu)", (unsigned long long)lens[j], j);
+      return SV_ERR_LEN;
+    }
+    longest = std::max<size_t>(longest, lens[j]);
+  }
+  if (!host::f_is_reduced(fe_in(*z), host::R64)) {
+    sv::set_error("z not reduced mod the scalar field order");
+    return SV_ERR_ARG;
+  }
+  if (!host::f_is_reduced(fe_in(*v), host::R64)) {
+    sv::set_error("v not reduced mod the scalar field order");
+    return SV_ERR_ARG;
+  }
+  *N = longest;
+  return SV_OK;
+}
+
+// The pass on a leased workspace: the table goes up from pinned staging in one copy on the call's
+// stream, the head (flag, evaluations) comes back behind the kernels.  ws->buf must hold
+// batch_device_bytes(m, N) from `at`; the pinned staging is reserved here.  Nothing is synchronised:
+// batch_result reads the head once the stream has drained.
+size_t batch_table_bytes(size_t m) { return Workspace::aligned(m * sizeof(BatchRow)); }
+size_t batch_device_bytes(size_t m, size_t N) {
+  return batch_table_bytes(m) + Workspace::aligned(poly_batch_scratch_bytes(m, N));
+}
+int batch_enqueue(Workspace* ws, size_t at, const sv_fe* const* d_polys, const uint64_t* lens, size_t m, size_t N,
+                  const sv_fe* z, const sv_fe* v, int form, int c_form, void* d_combined) {
+  const size_t tb = batch_table_bytes(m);
+  SV_TRY(ws->reserve_pinned(tb + poly_batch_head_bytes(m)));
+  BatchRow* rows = reinterpret_cast<BatchRow*>(ws->pinned);
+  poly_batch_fill_table(rows, d_polys, lens, m, *v, form);
+  char* d_table = ws->buf + at;
+  char* d_scratch = d_table + tb;
+  SV_HIP(hipMemcpyAsync(d_table, rows, m * sizeof(BatchRow), hipMemcpyHostToDevice, ws->stream));
+  SV_TRY(poly_combine_eval_enqueue(reinterpret_cast<const BatchRow*>(d_table), m, N, *z, form, c_form, d_combined,
+                                   d_scratch, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned + tb, d_scratch, poly_batch_head_bytes(m), hipMemcpyDeviceToHost, ws->stream));
+  return SV_OK;
+}
+
+int batch_result(const Workspace* ws, size_t m, sv_fe* out_evals) {
+  const char* head = ws->pinned + batch_table_bytes(m);
+  uint32_t errv;
+  memcpy(&errv, head + kBatchErrOffset, 4);
+  if (errv) {
+    sv::set_error("invalid input: coefficient not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  memcpy(out_evals, head + kBatchEvalsOffset, m * sizeof(sv_fe));
+  return SV_OK;
+}
+}  // namespace
+
+int sv_bn254_fr_poly_combine_eval_device(const sv_fe* const* d_polys, const uint64_t* lens, size_t m, const sv_fe* z,
+                                         const sv_fe* v, int form, int device, void* stream, sv_fe* d_combined,
+                                         sv_fe* out_evals) noexcept {
+  SV_GUARD_BEGIN
+  size_t N = 0;
+  SV_TRY(batch_call_args(d_polys, lens, m, z, v, form, out_evals, out_evals, &N));
+  if (d_combined) {
+    const uintptr_t cb = (uintptr_t)d_combined;
+    if (cb % 16) {
+      sv::set_error("d_combined is not 16-byte aligned");
+      return SV_ERR_ARG;
+    }
+    for (size_t j = 0; j < m; j++) {
+      const uintptr_t pb = (uintptr_t)d_polys[j];
+      if (cb < pb + lens[j] * sizeof(sv_fe) && pb < cb + N * sizeof(sv_fe)) {
+        sv::set_error("d_combined overlaps polynomial %zu (other blocks still read it while one writes)", j);
+        return SV_ERR_ARG;
+      }
+    }
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, (hipStream_t)stream);
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  SV_TRY(ws->reserve(batch_device_bytes(m, N)));
+  SV_TRY(batch_enqueue(ws, 0, d_polys, lens, m, N, z, v, form, form, d_combined));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl.armed = false;
+  return batch_result(ws, m, out_evals);
+  SV_GUARD_END
+}
+
+int sv_bn254_kzg_open_batch_device(uint64_t handle, size_t offset, const sv_fe* const* d_polys, const uint64_t* lens,
+                                   size_t m, const sv_fe* z, const sv_fe* v, int form, void* stream, sv_fe* out_evals,
+                                   sv_g1_jacobian* out_witness_partial) noexcept {
+  SV_GUARD_BEGIN
+  size_t N = 0;
+  SV_TRY(batch_call_args(d_polys, lens, m, z, v, form, out_evals, out_witness_partial, &N));
+  BaseSet t;
+  if (!set_lookup(handle, &t)) return SV_ERR_ARG;
+  if (offset > t.n || N - 1 > t.n - offset) {
+    sv::set_error("rows [%zu, %zu + %zu) reach past base set %llu (%zu rows)", offset, offset, N - 1,
+                  (unsigned long long)handle, t.n);
+    return SV_ERR_ARG;
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(t.dev, (hipStream_t)stream);
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  // pooled scratch: the table and the pass's totals, then the division's; c and q side by side in
+  // the input buffer (the division reads c again while it writes q), both in Montgomery form
+  const size_t cbytes = Workspace::aligned(N * sizeof(sv_fe));
+  const size_t bbytes = batch_device_bytes(m, N);
+  SV_TRY(ws->reserve_in(cbytes + Workspace::aligned((N - 1) * sizeof(sv_fe) + 1)));
+  SV_TRY(ws->reserve(bbytes + Workspace::aligned(poly_div_scratch_bytes(N))));
+  void* d_comb = ws->inbuf;
+  void* d_quot = ws->inbuf + cbytes;
+  SV_TRY(batch_enqueue(ws, 0, d_polys, lens, m, N, z, v, form, SV_MONTGOMERY, N > 1 ? d_comb : nullptr));
+  Xyzz w = host::x_identity();
+  if (N > 1) {  // the MSM synchronises the stream, so the head has landed when it returns
+    const sv_fe zm = form == SV_MONTGOMERY ? *z : poly_fr_to_mont(*z);  // c is Montgomery, so z goes with it
+    SV_TRY(poly_div_linear_enqueue(d_comb, N, zm, SV_MONTGOMERY, SV_MONTGOMERY, d_quot, ws->buf + bbytes, ws->stream));
+    const MsmResident set{t.rows, t.vtab, t.n, offset};
+    SV_TRY(msm_run_resident_device(set, d_quot, N - 1, SV_MONTGOMERY, t.dev, ws->stream, &w));
+  } else {
+    SV_HIP(hipStreamSynchronize(ws->stream));
+  }
+  dl.armed = false;
+  SV_TRY(batch_result(ws, m, out_evals));
+  jacobian_out(w, out_witness_partial);
+  return SV_OK;
+  SV_GUARD_END
+}
+
 int sv_bn254_poseidon_permute(sv_fe* states, size_t n, int t, int form) noexcept {
   SV_GUARD_BEGIN
   SV_TRY(check_form(form));

@@ -25,6 +25,19 @@
 // 4-bank slots); phase 3 stages the quotient the same way back.  The image (36 KiB) is reused for
 // the scan's two buffers, so four blocks fit a CU.  Traffic: the coefficients are read twice and
 // the quotient written once, 96 B per coefficient.
+//
+// Several polynomials at one point (a GWC19 point set: c = sum_j v^j p_j, e_j = p_j(z), one witness
+// for c) take one more pass in front of the division, in two launches of the same kind:
+//   k_batch_pass   block b walks the m polynomials over its span: per polynomial a Horner per
+//                  thread and a weighted TREE over the block (an evaluation needs a reduction, not
+//                  a scan: 1.25 products per coefficient against the scan's 3) into a per-block
+//                  total, and c's span accumulated in registers (one product per coefficient),
+//                  written once at the end.  Every polynomial is read once;
+//   k_batch_fold   block j folds polynomial j's totals with the weight z^S into e_j.
+// The polynomials' pointers, lengths and the powers of v are a per-call table in pooled scratch (one
+// H2D copy), not kernel arguments; z's weights are the division's.  Lengths may differ: N = the
+// longest, a shorter polynomial is zero past its end (inside a span) and skipped in the spans behind
+// it.  Traffic: (m + 1) x 32 B per coefficient.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -207,6 +220,141 @@ __global__ void __launch_bounds__(kNT) k_div_quotient(const uint4* __restrict__ 
   }
 }
 
+// ---- several polynomials at one point (poly_combine_eval_enqueue) ----
+// The weighted sum sum_t w^t v_t over the block's threads, w = step[0] and step[l] = w^(2^l): a tree
+// whose level l folds neighbouring pairs of the 256 >> l values left by the level before, with the
+// working threads packed at the front (128, 64, 32, ... of them, so 9 wave products instead of the
+// suffix scan's 32).  Thread 0 returns the sum; the last barrier comes after every read of sm, so
+// the caller may overwrite sm at once.
+__device__ __forceinline__ Fr block_weighted_sum(uint4* sm, Fr v, const Fr (&step)[kLevels]) {
+  const int t = (int)threadIdx.x;
+  uint4* cur = sm;
+  uint4* nxt = sm + kScanQ;
+  st_fr(cur + 2 * t, v);
+  __syncthreads();
+#pragma unroll
+  for (int l = 0; l < kLevels; l++) {
+    if (t < (kNT >> (l + 1))) {
+      v = ld_fr(cur + 4 * t) + step[l] * ld_fr(cur + 4 * t + 2);
+      st_fr(nxt + 2 * t, v);
+    }
+    __syncthreads();
+    uint4* s = cur;
+    cur = nxt, nxt = s;
+  }
+  return v;
+}
+
+// load_span in two halves, so that the next polynomial's loads are in flight during this one's
+// products: the span's uint4 [q0, q0 + 2 S) of src into registers, zeros past qn ...
+__device__ __forceinline__ void fetch_span(uint4 (&v)[2 * kT], const uint4* __restrict__ src, uint64_t q0, uint64_t qn) {
+#pragma unroll
+  for (int k = 0; k < 2 * kT; k++) {
+    const uint64_t g = q0 + threadIdx.x + k * kNT;
+    v[k] = g < qn ? src[g] : make_uint4(0, 0, 0, 0);
+  }
+}
+// ... and from there into the padded image
+__device__ __forceinline__ void store_span(uint4* sm, const uint4 (&v)[2 * kT]) {
+#pragma unroll
+  for (int k = 0; k < 2 * kT; k++) sm[image_slot((int)threadIdx.x + k * kNT)] = v[k];
+}
+
+// Block b walks the m polynomials over its span [b S, (b + 1) S): per polynomial the span's total
+// B_jb = sum_k a_j[b S + k] z^k (a Horner per thread, then the tree) into totals[j nb + b], and the
+// span of c = sum_j v^j a_j in registers (kCombine), stored once at the end.  A polynomial that ends
+// before the span is skipped (its totals there are never read); one that ends inside it is zero
+// past its end.  Every raw coefficient is checked below r; the block's flag is a plain store.
+// (The form is a template parameter: with a run-time branch around the conversion inside the loop
+// the compiler kept both versions of the four products alive to the loop's end, 300 registers.)
+template <bool kCombine, bool kMont>
+__global__ void __launch_bounds__(kNT) k_batch_pass(const BatchRow* __restrict__ table, uint32_t m, uint64_t N,
+                                                     const DivWeights w, int c_mont,
+                                                     uint4* __restrict__ combined, Fr* __restrict__ totals,
+                                                     uint32_t* __restrict__ flags) {
+  __shared__ uint4 sm[kImageQ];
+  const int t = (int)threadIdx.x;
+  const uint32_t nb = gridDim.x;
+  const uint64_t first = (uint64_t)blockIdx.x * kDivSpan;  // the span's first coefficient
+  const uint64_t q0 = 2 * first;
+  Fr c[kT];
+#pragma unroll
+  for (int k = 0; k < kT; k++) c[k] = Fr::zero();
+  bool bad = false;
+  uint4 v[2 * kT];
+  fetch_span(v, static_cast<const uint4*>(table[0].coeffs), q0, 2 * table[0].len);
+  for (uint32_t j = 0; j < m; j++) {
+    const bool live = table[j].len > first;  // the same for the whole block
+    if (live) {
+      store_span(sm, v);
+      __syncthreads();
+    }
+    if (j + 1 < m) fetch_span(v, static_cast<const uint4*>(table[j + 1].coeffs), q0, 2 * table[j + 1].len);
+    if (!live) continue;
+    Fr vp;
+    if (kCombine) memcpy(vp.v, table[j].vpow.l, sizeof vp.v);
+    Fr acc = Fr::zero();
+#pragma unroll
+    for (int k = kT - 1; k >= 0; k--) {
+      Fr a = ld_fr(sm + t * kChunkQ + 2 * k);
+      bad |= !a.is_reduced();
+      if (!kMont) a = fe_to_mont(a);
+      acc = k == kT - 1 ? a : a + w.z * acc;
+      if (kCombine) {
+        c[k] = c[k] + vp * a;
+        // pin the sum here: left alone, the compiler sinks the four additions to the loop's end and
+        // keeps the four products alive across the tree (300 registers, one wave per SIMD)
+#pragma unroll
+        for (int i = 0; i < 8; i++) asm volatile("" : "+v"(c[k].v[i]));
+      }
+    }
+    __syncthreads();  // the image is consumed: the tree reuses it
+    acc = block_weighted_sum(sm, acc, w.step);
+    if (t == 0) totals[(uint64_t)j * nb + blockIdx.x] = acc;
+  }
+  const int any_bad = __syncthreads_or(bad);
+  if (t == 0) flags[blockIdx.x] = any_bad ? 1u : 0u;
+  if (kCombine) {
+#pragma unroll
+    for (int k = 0; k < kT; k++) st_fr(sm + t * kChunkQ + 2 * k, c_mont ? c[k] : fe_from_mont(c[k]));
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2 * kT; k++) {
+      const int q = t + k * kNT;
+      if (q0 + q < 2 * N) combined[q0 + q] = sm[image_slot(q)];
+    }
+  }
+}
+
+// Block j folds polynomial j's totals: e_j = sum_b (z^S)^b B_jb over its ceil(len_j / S) spans, with
+// c = ceil(nb / kNT) consecutive totals per thread (the call's c, whatever the polynomial's length,
+// so one set of weights serves every block) and the tree over the threads.  Block 0 also folds
+// the flags.
+__global__ void __launch_bounds__(kNT) k_batch_fold(const BatchRow* __restrict__ table, uint32_t nb,
+                                                     const CarryWeights w, int mont, const Fr* __restrict__ totals,
+                                                     const uint32_t* __restrict__ flags, Fr* __restrict__ evals,
+                                                     uint32_t* __restrict__ err) {
+  __shared__ uint4 sm[2 * kScanQ];
+  const int t = (int)threadIdx.x;
+  const uint32_t j = blockIdx.x;
+  const uint32_t nbj = (uint32_t)((table[j].len + kDivSpan - 1) / kDivSpan);
+  const uint32_t c = (nb + kNT - 1) / kNT;
+  const uint32_t lo = (uint32_t)t * c;
+  const Fr* mine = totals + (uint64_t)j * nb;
+  Fr acc = Fr::zero();
+  uint32_t bad = 0;
+  for (uint32_t k = c; k-- > 0;) {
+    if (lo + k < nbj) acc = mine[lo + k] + w.W * acc;  // totals past nbj are zero, and come first
+    if (j == 0 && lo + k < nb) bad |= flags[lo + k];
+  }
+  const int any_bad = __syncthreads_or((int)bad);
+  acc = block_weighted_sum(sm, acc, w.step);
+  if (t == 0) {
+    evals[j] = mont ? acc : fe_from_mont(acc);
+    if (j == 0) *err = any_bad ? 1u : 0u;
+  }
+}
+
 // x^e by square and multiply (host: the per-call weights)
 Fr pow_u32(const Fr& x, uint32_t e) {
   Fr r = Fr::one();
@@ -215,6 +363,25 @@ Fr pow_u32(const Fr& x, uint32_t e) {
     if ((e >> bit) & 1u) r = r * x;
   }
   return r;
+}
+
+// the weights of a call over nb spans: z^T, squared per level up to z^(T 2^kLevels) = z^S, then
+// (z^S)^c and its squares, c = ceil(nb / threads) totals per thread
+void make_weights(const sv_fe& z, int mont, uint32_t nb, DivWeights* dw, CarryWeights* cw) {
+  memcpy(dw->z.v, z.l, sizeof dw->z.v);
+  if (!mont) dw->z = fe_to_mont(dw->z);
+  Fr x = dw->z;
+  for (int i = 0; i < ilog2(kDivPer); i++) x = fe_sqr(x);
+  for (int l = 0; l < kLevels; l++) {
+    dw->step[l] = x;
+    x = fe_sqr(x);
+  }
+  cw->W = x;
+  x = pow_u32(x, (nb + kDivThreads - 1) / kDivThreads);
+  for (int l = 0; l < kLevels; l++) {
+    cw->step[l] = x;
+    x = fe_sqr(x);
+  }
 }
 
 }  // namespace
@@ -239,29 +406,70 @@ int poly_div_linear_enqueue(const void* d_coeffs, size_t n, const sv_fe& z, int 
   Fr* carries = totals + nb;
   uint32_t* flags = reinterpret_cast<uint32_t*>(carries + nb);
   const int mont = form == SV_MONTGOMERY ? 1 : 0;
-  // the weights: z^T, squared per level up to z^(T 2^kLevels) = z^S, then (z^S)^c and its squares
   DivWeights dw;
-  memcpy(dw.z.v, z.l, sizeof dw.z.v);
-  if (!mont) dw.z = fe_to_mont(dw.z);
-  Fr x = dw.z;
-  for (int i = 0; i < ilog2(kDivPer); i++) x = fe_sqr(x);
-  for (int l = 0; l < kLevels; l++) {
-    dw.step[l] = x;
-    x = fe_sqr(x);
-  }
   CarryWeights cw;
-  cw.W = x;
-  x = pow_u32(x, (nb + kDivThreads - 1) / kDivThreads);
-  for (int l = 0; l < kLevels; l++) {
-    cw.step[l] = x;
-    x = fe_sqr(x);
-  }
+  make_weights(z, mont, nb, &dw, &cw);
   const uint4* c = static_cast<const uint4*>(d_coeffs);
   hipLaunchKernelGGL(k_div_reduce, dim3(nb), dim3(kNT), 0, st, c, (uint64_t)n, dw, mont, totals, flags);
   hipLaunchKernelGGL(k_div_carries, dim3(1), dim3(kNT), 0, st, totals, flags, nb, cw, mont, carries, eval, err);
   if (d_quotient && n > 1)
     hipLaunchKernelGGL(k_div_quotient, dim3(nb), dim3(kNT), 0, st, c, (uint64_t)n, dw, mont, carries,
                        q_form == SV_MONTGOMERY ? 1 : 0, static_cast<uint4*>(d_quotient));
+  SV_HIP(hipGetLastError());
+  return SV_OK;
+}
+
+sv_fe poly_fr_to_mont(const sv_fe& canonical) {
+  Fr x;
+  memcpy(x.v, canonical.l, sizeof x.v);
+  x = fe_to_mont(x);
+  sv_fe out;
+  memcpy(out.l, x.v, sizeof x.v);
+  return out;
+}
+
+void poly_batch_fill_table(BatchRow* rows, const sv_fe* const* d_polys, const uint64_t* lens, size_t m, const sv_fe& v,
+                           int form) {
+  Fr vm;
+  memcpy(vm.v, v.l, sizeof vm.v);
+  if (form != SV_MONTGOMERY) vm = fe_to_mont(vm);
+  Fr p = Fr::one();
+  for (size_t j = 0; j < m; j++) {
+    rows[j].coeffs = d_polys[j];
+    rows[j].len = lens[j];
+    memcpy(rows[j].vpow.l, p.v, sizeof p.v);
+    p = p * vm;
+  }
+}
+
+size_t poly_batch_scratch_bytes(size_t m, size_t N) {
+  const size_t nb = (N + kDivSpan - 1) / kDivSpan;
+  return poly_batch_head_bytes(m) + m * nb * sizeof(Fr) + nb * sizeof(uint32_t);
+}
+
+int poly_combine_eval_enqueue(const BatchRow* d_table, size_t m, size_t N, const sv_fe& z, int form, int c_form,
+                              void* d_combined, void* d_scratch, hipStream_t st) {
+  if (m == 0 || m > SV_OPEN_BATCH_MAX || N == 0 || N > (size_t(1) << 26)) {
+    set_error("poly_combine_eval: m = %zu, N = %zu out of range", m, N);
+    return SV_ERR_LEN;
+  }
+  const uint32_t nb = (uint32_t)((N + kDivSpan - 1) / kDivSpan);
+  char* scratch = static_cast<char*>(d_scratch);
+  uint32_t* err = reinterpret_cast<uint32_t*>(scratch + kBatchErrOffset);
+  Fr* evals = reinterpret_cast<Fr*>(scratch + kBatchEvalsOffset);
+  Fr* totals = evals + m;
+  uint32_t* flags = reinterpret_cast<uint32_t*>(totals + m * (size_t)nb);
+  const int mont = form == SV_MONTGOMERY ? 1 : 0;
+  const int c_mont = c_form == SV_MONTGOMERY ? 1 : 0;
+  DivWeights dw;
+  CarryWeights cw;
+  make_weights(z, mont, nb, &dw, &cw);
+  auto pass = d_combined ? (mont ? k_batch_pass<true, true> : k_batch_pass<true, false>)
+                         : (mont ? k_batch_pass<false, true> : k_batch_pass<false, false>);
+  hipLaunchKernelGGL(pass, dim3(nb), dim3(kNT), 0, st, d_table, (uint32_t)m, (uint64_t)N, dw, c_mont,
+                     static_cast<uint4*>(d_combined), totals, flags);
+  hipLaunchKernelGGL(k_batch_fold, dim3((uint32_t)m), dim3(kNT), 0, st, d_table, nb, cw, mont, totals, flags, evals,
+                     err);
   SV_HIP(hipGetLastError());
   return SV_OK;
 }

@@ -11,7 +11,7 @@ All compute runs in libsvgpu.so (HIP, gfx950); there is no CPU fallback.
 """
 from ._lib import (SV_CANONICAL, SV_MONTGOMERY, ArgumentError, DeviceError, EmptyError, LengthError,
                    OutOfMemoryError, SvError, lib)
-from .kzg import AssertionFailure, KzgAccumulator, KzgAs, KzgDecidingKey
+from .kzg import AssertionFailure, KzgAccumulator, KzgAs, KzgDecidingKey, gwc19_open, gwc19_query_sets
 from .loader import (BaseTable, NativeLoader, ReferencePanic, ResidentBases, batch_multi_scalar_multiplication,
                      fold_partials, msm_arrays, make_refs, msm_batch_arrays, msm_refs, multi_scalar_multiplication)
 from .poseidon import Poseidon, PoseidonTranscript
@@ -27,6 +27,12 @@ def poly_div_linear_device(coeffs, z, **kwargs):
     """svgpu.device.poly_div_linear_device (imported on first use: that module needs torch)."""
     from .device import poly_div_linear_device as run
     return run(coeffs, z, **kwargs)
+
+
+def poly_combine_eval_device(polys, z, v, **kwargs):
+    """svgpu.device.poly_combine_eval_device (imported on first use: that module needs torch)."""
+    from .device import poly_combine_eval_device as run
+    return run(polys, z, v, **kwargs)
 
 
 def version() -> str:

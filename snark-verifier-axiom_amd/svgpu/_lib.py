@@ -18,6 +18,8 @@ SV_MONTGOMERY = 1
 
 SV_OK, SV_ERR_EMPTY, SV_ERR_LEN, SV_ERR_ARG, SV_ERR_DEVICE, SV_ERR_OOM = range(6)
 
+SV_OPEN_BATCH_MAX = 4096  # polynomials per batched opening
+
 SV_ENC_HALO2_COMPRESSED = 0
 SV_ENC_EVM = 1
 
@@ -124,6 +126,10 @@ PROTOTYPES = [
                                    POINTER(sv_g1_affine)]),
     ("sv_bn254_kzg_open_device", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, POINTER(sv_fe), c_int, c_void_p,
                                           POINTER(sv_fe), POINTER(sv_g1_jacobian)]),
+    ("sv_bn254_fr_poly_combine_eval_device", c_int, [c_void_p, c_void_p, c_size_t, POINTER(sv_fe), POINTER(sv_fe),
+                                                      c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("sv_bn254_kzg_open_batch_device", c_int, [c_uint64, c_size_t, c_void_p, c_void_p, c_size_t, POINTER(sv_fe),
+                                                POINTER(sv_fe), c_int, c_void_p, c_void_p, POINTER(sv_g1_jacobian)]),
     ("sv_bn254_poseidon_permute", c_int, [c_void_p, c_size_t, c_int, c_int]),
     ("sv_bn254_poseidon_permute_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_squeeze", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

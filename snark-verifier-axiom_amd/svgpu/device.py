@@ -97,6 +97,58 @@ def poly_div_linear_device(coeffs: torch.Tensor, z: int, form: int = _lib.SV_MON
     return enc.fr_from_struct(ev, form), (out[:n - 1] if quotient else None)
 
 
+def batch_tables(polys):
+    """The host arrays of a batched call: (tensors kept alive, c_void_p[m] device pointers,
+    c_uint64[m] lengths) for a list of (n_j, 4) int64 tensors on one GPU."""
+    keep = []
+    for p in polys:
+        if p.device.type != "cuda":
+            raise _lib.DeviceError("tensor must live on a GPU (cuda/HIP device)")
+        if p.dtype != torch.int64 or p.dim() != 2 or p.shape[1] != 4:
+            raise _lib.ArgumentError("a polynomial is an (n, 4) int64 tensor of limbs")
+        if keep and p.device != keep[0].device:
+            raise _lib.ArgumentError("the polynomials of a batch live on one device")
+        keep.append(p.contiguous())
+    m = len(keep)
+    ptrs = (ctypes.c_void_p * max(m, 1))(*[p.data_ptr() for p in keep])
+    lens = (ctypes.c_uint64 * max(m, 1))(*[p.shape[0] for p in keep])
+    return keep, ptrs, lens
+
+
+def combine_eval_pointers(ptrs, lens, m: int, z: int, v: int, form: int, device: int, stream, combined_ptr) -> List[int]:
+    """sv_bn254_fr_poly_combine_eval_device over raw host arrays of device pointers and lengths
+    (what poly_combine_eval_device builds from tensors) -> the m evaluations as canonical ints."""
+    zs, vs = enc.fr_struct(z, form), enc.fr_struct(v, form)
+    ev = (_lib.sv_fe * max(m, 1))()
+    _lib.check(_lib.lib.sv_bn254_fr_poly_combine_eval_device(ptrs, lens, m, ctypes.byref(zs), ctypes.byref(vs), form,
+                                                             device, stream, combined_ptr, ev),
+               "sv_bn254_fr_poly_combine_eval_device")
+    return [enc.fr_from_struct(ev[j], form) for j in range(m)]
+
+
+def poly_combine_eval_device(polys, z: int, v: int, form: int = _lib.SV_MONTGOMERY, combined: bool = True,
+                             out: torch.Tensor = None) -> Tuple[List[int], Optional[torch.Tensor]]:
+    """One GWC19 point set without the witness: for the HBM-resident polynomials p_j ((n_j, 4) int64
+    limbs in `form`; z and v canonical ints) -> ([p_j(z)] as canonical ints, c = sum_j v^j p_j as
+    N = max n_j rows in `form`, or None with combined=False: evaluate only).  A shorter polynomial is
+    zero past its end; `out` (at least N rows) must not overlap a polynomial."""
+    keep, ptrs, lens = batch_tables(polys)
+    m = len(keep)
+    n = max((p.shape[0] for p in keep), default=0)
+    d, stream, dev = 0, None, None
+    if m:
+        dev = keep[0].device
+        d, stream = _dev_index(keep[0]), _stream_handle(dev)
+    if combined and out is None and m:
+        out = torch.empty((max(n, 1), 4), dtype=torch.int64, device=dev)
+    elif combined and m and (out.device != dev or out.dtype != torch.int64 or not out.is_contiguous()
+                             or out.dim() != 2 or out.shape[1] != 4 or out.shape[0] < n):
+        raise _lib.LengthError(f"poly_combine_eval: out must be a contiguous (>= {n}, 4) int64 tensor on {dev}")
+    evals = combine_eval_pointers(ptrs, lens, m, z, v, form, d, stream,
+                                  out.data_ptr() if combined and out is not None else None)
+    return evals, (out[:n] if combined else None)
+
+
 def last_msm_stats() -> dict:
     s = _lib.sv_msm_stats()
     _lib.check(_lib.lib.sv_msm_last_stats(ctypes.byref(s)), "sv_msm_last_stats")

@@ -148,3 +148,36 @@ class KzgAs:
         """AccumulationScheme::verify (accumulation.rs:40-62): the same transcript and MSMs."""
         return KzgAs.create_proof(instances, transcript)
 
+
+def gwc19_query_sets(queries: Sequence[Tuple[int, int]]) -> list:
+    """The point sets of a GWC19 opening, grouped as the reference's query_sets does
+    (snark-verifier/src/pcs/kzg/multiopen/gwc19.rs:140-158): sets in order of the first appearance of
+    a shift, each with its polynomials in query order -> [(shift, [poly index], [query index])]."""
+    sets: list = []
+    for qi, (poly, shift) in enumerate(queries):
+        for s in sets:
+            if s[0] == shift:
+                s[1].append(poly)
+                s[2].append(qi)
+                break
+        else:
+            sets.append((shift, [poly], [qi]))
+    return sets
+
+
+def gwc19_open(rset, polys, queries: Sequence[Tuple[int, int]], z: int, v: int, offset: int = 0,
+               form: int = _lib.SV_MONTGOMERY) -> Tuple[list, list]:
+    """The prover's side of Gwc19::verify (gwc19.rs:43-80) on a resident base set: `polys` are
+    (n_j, 4) int64 torch tensors in `form` in HBM on the set's device, `queries` a list of
+    (poly index, shift), z and v canonical ints.  Point set i (gwc19_query_sets) is opened at
+    shift_i * z with one batched call -- W_i = the witness of sum_j v^j p_ij there -- so the several
+    points of an opening cost one MSM each, however many polynomials share a point.
+    Returns ([evaluation per query, in query order], [W_i per set])."""
+    evals = [None] * len(queries)
+    witnesses = []
+    for shift, members, where in gwc19_query_sets(queries):
+        es, w = rset.open_batch_device([polys[j] for j in members], shift * z % enc.R, v, offset=offset, form=form)
+        for qi, e in zip(where, es):
+            evals[qi] = e
+        witnesses.append(w)
+    return evals, witnesses

@@ -327,6 +327,46 @@ class ResidentBases:
                    "sv_bn254_g1_fold")
         return enc.fr_from_struct(ev, form), enc.g1_from_struct(out)
 
+    def open_batch_pointers(self, ptrs, lens, m: int, z: int, v: int, offset: int, form: int,
+                            stream) -> Tuple[list, Point]:
+        """sv_bn254_kzg_open_batch_device over raw host arrays of m device pointers and lengths (what
+        open_batch_device builds from tensors) -> ([p_j(z)], witness), canonical."""
+        if self.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        zs, vs = enc.fr_struct(z, form), enc.fr_struct(v, form)
+        ev, part = (_lib.sv_fe * max(m, 1))(), _lib.sv_g1_jacobian()
+        _lib.check(_lib.lib.sv_bn254_kzg_open_batch_device(self.handle, offset, ptrs, lens, m, ctypes.byref(zs),
+                                                           ctypes.byref(vs), form, stream, ev, ctypes.byref(part)),
+                   "sv_bn254_kzg_open_batch_device")
+        out = _lib.sv_g1_affine()
+        _lib.check(_lib.lib.sv_bn254_g1_fold(ctypes.byref(part), 1, ctypes.byref(out), _lib.SV_CANONICAL),
+                   "sv_bn254_g1_fold")
+        return [enc.fr_from_struct(ev[j], form) for j in range(m)], enc.g1_from_struct(out)
+
+    def open_batch_device(self, polys, z: int, v: int, offset: int = 0,
+                          form: int = _lib.SV_MONTGOMERY) -> Tuple[list, Point]:
+        """One GWC19 point set: the polynomials p_j ((n_j, 4) int64 torch tensors in `form`, in HBM on
+        the set's device) opened at z under the challenge v -> ([p_j(z)], witness), canonical, with
+        witness = sum_k q_k set[offset + k] for q = (c - c(z)) / (X - z), c = sum_j v^j p_j: one pass
+        over the polynomials, one division and ONE MSM, whatever m is."""
+        if self.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        from . import device as dv
+        keep, ptrs, lens = dv.batch_tables(polys)
+        stream = dv._stream_handle(keep[0].device) if keep else None
+        return self.open_batch_pointers(ptrs, lens, len(keep), z, v, offset, form, stream)
+
+    def open_batch_arrays(self, polys, z: int, v: int, offset: int = 0,
+                          form: int = _lib.SV_CANONICAL) -> Tuple[list, Point]:
+        """The same for host coefficients ((n_j, 4) u64 numpy arrays in `form`): uploaded with torch to
+        the set's device, then the device path (the library has no host-fed batch)."""
+        if self.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        import torch
+        up = [torch.from_numpy(np.ascontiguousarray(p, dtype=np.uint64).view(np.int64)).to(f"cuda:{self.device}")
+              for p in polys]
+        return self.open_batch_device(up, z, v, offset=offset, form=form)
+
 
 def batch_multi_scalar_multiplication(msms: Sequence[Sequence[Tuple[int, Point]]]) -> list:
     """[NativeLoader.multi_scalar_multiplication(pairs) for pairs in msms], one GPU launch."""

@@ -158,6 +158,14 @@ extern "C" {
     pub fn sv_bn254_kzg_open_device(handle: u64, offset: usize, d_coeffs: *const SvFe, n: usize, z: *const SvFe,
                                     form: c_int, stream: *mut c_void, out_eval: *mut SvFe,
                                     out_witness_partial: *mut SvG1Jacobian) -> c_int;
+    pub fn sv_bn254_fr_poly_combine_eval_device(d_polys: *const *const SvFe, lens: *const u64, m: usize,
+                                                z: *const SvFe, v: *const SvFe, form: c_int, device: c_int,
+                                                stream: *mut c_void, d_combined: *mut SvFe,
+                                                out_evals: *mut SvFe) -> c_int;
+    pub fn sv_bn254_kzg_open_batch_device(handle: u64, offset: usize, d_polys: *const *const SvFe,
+                                          lens: *const u64, m: usize, z: *const SvFe, v: *const SvFe,
+                                          form: c_int, stream: *mut c_void, out_evals: *mut SvFe,
+                                          out_witness_partial: *mut SvG1Jacobian) -> c_int;
     pub fn sv_bn254_poseidon_permute(states: *mut SvFe, n: usize, t: c_int, form: c_int) -> c_int;
     pub fn sv_bn254_poseidon_permute_device(d_states: *mut SvFe, n: usize, t: c_int, form: c_int, device: c_int,
                                             stream: *mut c_void) -> c_int;
@@ -522,6 +530,31 @@ impl ResidentBases {
                               &mut out)
         };
         (rc == SV_OK).then(|| (eval, g1_out(out)))
+    }
+
+    /// One GWC19 point set (gwc19.rs:43-80, the prover's side): the polynomials at `d_polys`
+    /// (device pointers to Montgomery coefficients on the set's device, `lens[j]` of them each)
+    /// opened at z under the challenge v: ([p_j(z)], witness) with witness = Σ q_k · set[offset + k]
+    /// for q = (c − c(z)) / (X − z), c = Σ v^j · p_j.  One pass over the polynomials, one division
+    /// and one MSM, whatever their number; `stream` may be null.
+    ///
+    /// # Safety
+    /// Every `d_polys[j]` must point to `lens[j]` readable elements in device memory.
+    pub unsafe fn open_batch_device(&self, offset: usize, d_polys: &[*const Fr], lens: &[u64], z: &Fr, v: &Fr,
+                                    stream: *mut c_void) -> Option<(Vec<Fr>, G1Affine)> {
+        assert_eq!(d_polys.len(), lens.len());
+        let mut evals = vec![Fr::zero(); d_polys.len()];
+        let mut part = SvG1Jacobian::default();
+        let rc = sv_bn254_kzg_open_batch_device(self.handle, offset, d_polys.as_ptr() as *const *const SvFe,
+                                                lens.as_ptr(), d_polys.len(), z as *const Fr as *const SvFe,
+                                                v as *const Fr as *const SvFe, SV_MONTGOMERY, stream,
+                                                evals.as_mut_ptr() as *mut SvFe, &mut part);
+        if rc != SV_OK {
+            return None;
+        }
+        let mut out = SvG1Affine::default();
+        let rc = sv_bn254_g1_fold(&part, 1, &mut out, SV_MONTGOMERY);
+        (rc == SV_OK).then(|| (evals, g1_out(out)))
     }
 }
 
