@@ -82,7 +82,15 @@ __device__ __forceinline__ Fr ld_const(const uint32_t* p) {
 //   * a partial round's state[i] += col_hat[i-1] * state[0] adds a product below 1.38 r and wraps
 //     at 2r, so it never grows past max(2r, its previous bound).
 // The last full round reduces its rows once (below 1.32 r) and the result is canonicalised.  t = 5
-// rows (two fused sums and an addition) keep fe_mul_sum's subtraction.
+// rows (two fused sums and an addition) keep fe_mul_sum's subtraction, but their words come in below
+// 2 r (after fe_add2p), not below r: the three-product sum scans below (3 * 2 * 0.18905 + 1) r
+// = 2.14 r and loses r once, the two-product sum stays below r, and operator+ takes r off their sum
+// once, so a t = 5 row leaves below 1.14 r -- for constants anywhere below r possibly in
+// [r, 1.14 r).  That is consistent: pow5 takes words below 2.32 r, state[i] += .. wraps at 2 r, and
+// the fe_canon2p at the end of the permutation takes words below 2 r.  (With the real tables every
+// row leaves below r: it would take c_0 + c_1 + c_2 above 2^255, which no row has.
+// tests/test_gpu_poseidon_stages.py walks the schedule with the real constants and checks every
+// bound stated here, for both limb forms.)
 __device__ __forceinline__ Fr pow5(const Fr& x) {
   const Fr x2 = fe_sqr_hp<FrTag, false>(x);
   return fe_mul_lazy(fe_sqr_hp<FrTag, false>(x2), x);
@@ -126,6 +134,17 @@ __device__ __forceinline__ void full_round(Fr (&s)[T], const uint32_t* c, const 
   apply_mds<T, kLazy>(s, m);
 }
 
+// partial round r: sbox_part, then apply_sparse_mds (poseidon.rs:359-361, :399-412)
+template <int T>
+__device__ __forceinline__ void partial_round(Fr (&s)[T], int r) {
+  s[0] = fe_add2p(pow5(s[0]), ld_const(PSpec<T>::partial() + r * 8));
+  const uint32_t* row = PSpec<T>::sparse() + r * (2 * T - 1) * 8;
+  const Fr s0 = mds_row<T>(s, row);
+#pragma unroll
+  for (int i = 1; i < T; i++) s[i] = fe_add2p(s[i], fe_mul_lazy(s[0], ld_const(row + (T + i - 1) * 8)));
+  s[0] = s0;
+}
+
 // Poseidon::permutation (poseidon.rs:469-500) without the absorbed inputs: the bare HADES map.
 template <int T>
 __device__ __forceinline__ void permute(Fr (&s)[T]) {
@@ -135,17 +154,7 @@ __device__ __forceinline__ void permute(Fr (&s)[T]) {
   for (int i = 0; i < T; i++) s[i] = s[i] + ld_const(start + i * 8);  // absorb_with_pre_constants
   for (int r = 1; r < H; r++) full_round<T>(s, start + r * T * 8, PSpec<T>::mds());
   full_round<T>(s, start + H * T * 8, PSpec<T>::pre());
-  // partial rounds: sbox_part, then apply_sparse_mds (poseidon.rs:359-361, :399-412)
-  const uint32_t* partial = PSpec<T>::partial();
-  const uint32_t* sparse = PSpec<T>::sparse();
-  for (int r = 0; r < RP; r++) {
-    s[0] = fe_add2p(pow5(s[0]), ld_const(partial + r * 8));
-    const uint32_t* row = sparse + r * (2 * T - 1) * 8;
-    const Fr s0 = mds_row<T>(s, row);
-#pragma unroll
-    for (int i = 1; i < T; i++) s[i] = fe_add2p(s[i], fe_mul_lazy(s[0], ld_const(row + (T + i - 1) * 8)));
-    s[0] = s0;
-  }
+  for (int r = 0; r < RP; r++) partial_round<T>(s, r);
   const uint32_t* end = PSpec<T>::end();
   for (int r = 0; r < H - 1; r++) full_round<T>(s, end + r * T * 8, PSpec<T>::mds());
   full_round<T, false>(s, nullptr, PSpec<T>::mds());  // rows reduced once: below 1.32 r
@@ -190,6 +199,15 @@ __device__ __forceinline__ void full(E& a, E& b, E& c, const uint32_t* k, const 
   }
   mds(a, b, c, m);
 }
+// partial round r, state[1..] brought back below 4 r
+__device__ __forceinline__ void partial(E& a, E& b, E& c, int r) {
+  a = r29::add(pow5(a), ld(c_partial3_29 + r * 9));
+  const uint32_t* rw = c_sparse3_29 + r * 5 * 9;
+  const E a2 = row(a, b, c, rw);
+  b = r29::csub<4>(r29::add(b, r29::mul(a, ld(rw + 27))));
+  c = r29::csub<4>(r29::add(c, r29::mul(a, ld(rw + 36))));
+  a = a2;
+}
 __device__ __forceinline__ void permute(E& a, E& b, E& c) {
   constexpr int RF = SV_POSEIDON_T3_RF, RP = SV_POSEIDON_T3_RP, H = RF / 2;
   a = r29::add(a, ld(c_start3_29));
@@ -197,14 +215,7 @@ __device__ __forceinline__ void permute(E& a, E& b, E& c) {
   c = r29::add(c, ld(c_start3_29 + 18));
   for (int r = 1; r < H; r++) full(a, b, c, c_start3_29 + r * 27, c_mds3_29);
   full(a, b, c, c_start3_29 + H * 27, c_pre3_29);
-  for (int r = 0; r < RP; r++) {
-    a = r29::add(pow5(a), ld(c_partial3_29 + r * 9));
-    const uint32_t* rw = c_sparse3_29 + r * 5 * 9;
-    const E a2 = row(a, b, c, rw);
-    b = r29::csub<4>(r29::add(b, r29::mul(a, ld(rw + 27))));
-    c = r29::csub<4>(r29::add(c, r29::mul(a, ld(rw + 36))));
-    a = a2;
-  }
+  for (int r = 0; r < RP; r++) partial(a, b, c, r);
   for (int r = 0; r < H - 1; r++) full(a, b, c, c_end3_29 + r * 27, c_mds3_29);
   full(a, b, c, nullptr, c_mds3_29);
 }

@@ -224,7 +224,10 @@ def test_gt_equals_halo2curves_structured_restatement(gpu, oracle_cpp):
 def test_decider_prologue_variants(gpu, oracle_cpp, monkeypatch, env):
     """k_decide_wg's prologue options (the round-5 one-term-per-lane products and their round-4
     form, paired Miller steps, pair products from the key's constants) all give the oracle's Gt
-    values, verdicts and first failure -- identity points included."""
+    values, verdicts and first failure -- identity points included.
+    (SVGPU_DECIDER_KC is read once per process, on its first decide, so setting it here no longer
+    takes effect; tests/test_gpu_process_switches.py runs this case in a process started with
+    SVGPU_DECIDER_KC=0, which is what reaches the d_kc = nullptr path.)"""
     import svgpu
     from svgpu import device as dv
     from svgpu import encoding as enc

@@ -15,18 +15,34 @@ from oracle import poseidon as op
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("key", ["perm_x5_254_3", "perm_x5_254_5"])
-def test_permutation_kat(gpu, key):
+def _r29(monkeypatch, r29):
+    """SVGPU_POSEIDON_R29 (read per call): unset runs t = 3 on the 29-bit limbs, "0" on the
+    8 x 32-bit rounds (k_poseidon_permute<3, false> / k_poseidon_squeeze<3, false>)."""
+    if r29 is None:
+        monkeypatch.delenv("SVGPU_POSEIDON_R29", raising=False)
+    else:
+        monkeypatch.setenv("SVGPU_POSEIDON_R29", r29)
+
+
+# the 8 x 32-bit t = 3 rounds as extra cases; the ids of the default cases stay as they were
+_T_R29 = pytest.mark.parametrize("t,r29", [(3, None), (5, None), (3, "0")], ids=["3", "5", "3-R29=0"])
+
+
+@pytest.mark.parametrize("key,r29", [("perm_x5_254_3", None), ("perm_x5_254_5", None), ("perm_x5_254_3", "0")],
+                         ids=["perm_x5_254_3", "perm_x5_254_5", "perm_x5_254_3-R29=0"])
+def test_permutation_kat(gpu, monkeypatch, key, r29):
     from svgpu import poseidon as gp
+    _r29(monkeypatch, r29)
     k = load_golden("poseidon_kat.json")[key]
     out = gp.permute([[int(v) for v in k["input"]]], t=k["t"])
     assert out == [[int(v) for v in k["output"]]]
 
 
-@pytest.mark.parametrize("t", [3, 5])
-def test_permutation_random_both_forms(gpu, t):
+@_T_R29
+def test_permutation_random_both_forms(gpu, monkeypatch, t, r29):
     import svgpu
     from svgpu import _lib, device as dv, encoding as enc
+    _r29(monkeypatch, r29)
     rng = random.Random(7 + t)
     states = [[rng.randrange(b.R) for _ in range(t)] for _ in range(40)]
     states[0] = [0] * t
@@ -41,11 +57,23 @@ def test_permutation_random_both_forms(gpu, t):
     torch.cuda.synchronize()
     got = [enc._from_form(enc.limbs_to_int(r), b.R, _lib.SV_MONTGOMERY) for r in buf.cpu().numpy().view(np.uint64)]
     assert got == [v for s in want for v in s]
+    # the grid tail of a 256-thread block: one state, one short of a block, a block, one more
+    more = states + [[rng.randrange(b.R) for _ in range(t)] for _ in range(257 - len(states))]
+    want = [op.permutation(s, t, *op.PARAMS[t]) for s in more]
+    for n in (1, 255, 256, 257):
+        assert gp.permute(more[:n], t) == want[:n], n
+        buf = torch.from_numpy(enc.scalars_array([v for s in more[:n] for v in s], svgpu.SV_MONTGOMERY)
+                               .view(np.int64)).to(gpu)
+        dv.poseidon_permute(buf, t, _lib.SV_MONTGOMERY)
+        torch.cuda.synchronize()
+        got = [enc._from_form(enc.limbs_to_int(r), b.R, _lib.SV_MONTGOMERY) for r in buf.cpu().numpy().view(np.uint64)]
+        assert got == [v for s in want[:n] for v in s], n
 
 
-@pytest.mark.parametrize("t", [3, 5])
-def test_sponge_squeeze_lengths_and_continuation(gpu, t):
+@_T_R29
+def test_sponge_squeeze_lengths_and_continuation(gpu, monkeypatch, t, r29):
     from svgpu import poseidon as gp
+    _r29(monkeypatch, r29)
     rng = random.Random(100 + t)
     for length in range(0, 3 * t + 2):
         ref = op.Sponge(t)
@@ -60,8 +88,10 @@ def test_sponge_squeeze_lengths_and_continuation(gpu, t):
     assert dev.state == gp.Poseidon.default_state(t) and dev.buf == []
 
 
-def test_squeeze_many_ragged_batch(gpu):
+@pytest.mark.parametrize("r29", [None, "0"], ids=["R29", "R29=0"])
+def test_squeeze_many_ragged_batch(gpu, monkeypatch, r29):
     from svgpu import poseidon as gp
+    _r29(monkeypatch, r29)
     rng = random.Random(5)
     lens = [0, 1, 2, 3, 4, 7, 0, 11, 2, 64]
     refs, devs = [], []
