@@ -249,7 +249,8 @@ int sv_bn254_g1_msm_bases_device(uint64_t handle, size_t offset, const sv_fe* d_
  * are re-entrant on one handle like the other resident calls.
  * Not covered: host coefficients fed in pieces, high end first, so that the copy overlaps the scan
  * and the sort; multi-device sets.  Several polynomials at one point: the batched opening below;
- * several points: one batched opening per point (svgpu.kzg.gwc19_open groups the queries).      */
+ * several points: one batched opening per point (svgpu.kzg.gwc19_open groups the queries), or
+ * the SHPLONK opening further down, whose two MSMs do not grow with the number of points.        */
 int sv_bn254_fr_poly_div_linear_device(const sv_fe* d_coeffs, size_t n, const sv_fe* z, int form,
                                        int device, void* stream, sv_fe* d_quotient,
                                        sv_fe* out_eval) SV_NOEXCEPT;
@@ -288,7 +289,7 @@ int sv_bn254_kzg_open_device(uint64_t handle, size_t offset, const sv_fe* d_coef
  * device; the handle stays usable and nothing is retained.  Calls are re-entrant on one handle.
  * The pass keeps m * ceil(N / 1024) block totals (32 B each) in scratch: 2 MiB at m = 64, N = 2^20.
  * Not covered: a batch fed from host coefficients (a caller with host coefficients uploads them
- * first); the SHPLONK (bdfg21) prover; multi-device sets.                                       */
+ * first); multi-device sets.  The SHPLONK (bdfg21) prover: the block after this one.            */
 #define SV_OPEN_BATCH_MAX 4096 /* polynomials per call */
 int sv_bn254_fr_poly_combine_eval_device(const sv_fe* const* d_polys, const uint64_t* lens, size_t m,
                                          const sv_fe* z, const sv_fe* v, int form, int device,
@@ -297,6 +298,70 @@ int sv_bn254_kzg_open_batch_device(uint64_t handle, size_t offset, const sv_fe* 
                                    const uint64_t* lens, size_t m, const sv_fe* z, const sv_fe* v,
                                    int form, void* stream, sv_fe* out_evals,
                                    sv_g1_jacobian* out_witness_partial) SV_NOEXCEPT;
+
+/* ---- several points: evaluation, division by several roots, the SHPLONK (bdfg21) opening ----
+ * SHPLONK (snark-verifier/src/pcs/kzg/multiopen/bdfg21.rs, the SDK's default multi-open) groups
+ * the polynomials into sets i = 1..s whose members p_ij are all opened at the same points z_ik,
+ * k < K_i, and takes TWO witnesses whatever the number of points.  With challenges mu, gamma, z':
+ *   e_ijk = p_ij(z_ik);  c_i = sum_j mu^j p_ij;  h_i = the quotient of c_i by Z_i = prod_k (X - z_ik),
+ *   remainder dropped (0 when c_i has at most K_i coefficients);  h = sum_i gamma^i h_i (gamma^0 for
+ *   the first set);  W = sum_k h_k set[offset + k];
+ *   L = sum_i gamma^i Z_1(z') / Z_i(z') c_i - Z_1(z') h;  W' = sum_k q_k set[offset + k] for the
+ *   quotient q of L by (X - z'), remainder dropped.
+ * For set[k] = s^k g, lhs = f + z' W', rhs = W' is the accumulator of Bdfg21::verify (bdfg21.rs:47-79).
+ * All mod r and group sums: every output is determined bit for bit.
+ * fr_poly_eval_points_device: out_evals[j * K + k] = p_j(points[k]) for m polynomials in HBM and K
+ *   points in ONE pass that reads every polynomial once (up to 4 points per launch, K trees folded
+ *   per barrier; csrc/kzg_open.hip), where K single-point passes read them K times.  d_polys, lens
+ *   as for the batched opening; points and out_evals are host arrays; points may repeat.
+ * fr_poly_div_roots_device: d_quotient (n - K elements in HBM, `form`) = the quotient of the n
+ *   coefficients at d_coeffs by prod_k (X - roots[k]), remainder dropped: K runs of the division
+ *   above, Montgomery form in pooled scratch in between.  K == 1 is fr_poly_div_linear_device's
+ *   quotient bit for bit.  Roots may repeat.
+ * shplonk_quotient_device, shplonk_witness_device: the opening in two calls, because W enters the
+ *   transcript before z' exists.  Polynomials are given in set order: set i owns
+ *   d_polys[first_poly .. first_poly + num_polys) and points[first_point .. first_point + num_points),
+ *   and the sets partition both arrays in order.  d_work is CALLER-OWNED HBM on the set's device of
+ *   at least shplonk_work_elems elements (n_sets sets, N = the longest polynomial): the first call
+ *   leaves c_1 .. c_s and h there in Montgomery form (private layout), the second reads them, so the
+ *   library keeps no state between the calls.  The second call trusts the contents of d_work but
+ *   never reads outside work_elems; set_lens[i] = N_i, the longest polynomial of set i.  d_work must
+ *   not overlap a polynomial.  W takes max_i (N_i - K_i) rows of the set and no MSM when every h_i is
+ *   zero (the identity); W' takes N - 1 rows, and N == 1 gives the identity.  `form` covers
+ *   coefficients, points and challenges; the Jacobian partials are canonical.
+ * Checked before any device work, in this order: bad form, a null pointer, a misaligned
+ * d_polys[j], d_coeffs, d_quotient or d_work SV_ERR_ARG; m, K, n, n_sets or n_points == 0, any
+ * length 0, a set without polynomials or points SV_ERR_EMPTY; K (of the call or of a set) >
+ * SV_EVAL_POINTS_MAX, m or n_sets > SV_OPEN_BATCH_MAX, a length > 2^26 SV_ERR_LEN; a point or root,
+ * then mu, gamma, z' not below r SV_ERR_ARG ("not reduced"); div_roots: n <= K, then d_quotient
+ * overlapping d_coeffs SV_ERR_ARG; shplonk: sets that do not partition the arrays, two equal points
+ * inside one set ("repeated point"), z' equal to a point, work_elems too small, d_work over a
+ * polynomial, an unknown handle, a range beyond the set SV_ERR_ARG.  A coefficient not below r is
+ * SV_ERR_ARG ("not reduced") for that call, found on the device; the handle stays usable.  Calls
+ * are re-entrant on one handle and `stream` may be NULL.
+ * Not covered: multi-device sets; openings fed from host coefficients; a fused division by
+ * several roots (K suffix scans over one read).                                               */
+#define SV_EVAL_POINTS_MAX 16 /* points per evaluation call, roots per division, points per set */
+int sv_bn254_fr_poly_eval_points_device(const sv_fe* const* d_polys, const uint64_t* lens, size_t m,
+                                        const sv_fe* points, size_t K, int form, int device,
+                                        void* stream, sv_fe* out_evals) SV_NOEXCEPT;
+int sv_bn254_fr_poly_div_roots_device(const sv_fe* d_coeffs, size_t n, const sv_fe* roots, size_t K,
+                                      int form, int device, void* stream,
+                                      sv_fe* d_quotient) SV_NOEXCEPT;
+typedef struct { uint32_t first_poly, num_polys, first_point, num_points; } sv_shplonk_set;
+int sv_bn254_shplonk_work_elems(size_t n_sets, size_t N, uint64_t* elems) SV_NOEXCEPT;
+int sv_bn254_shplonk_quotient_device(uint64_t handle, size_t offset, const sv_fe* const* d_polys,
+                                     const uint64_t* lens, size_t m, const sv_shplonk_set* sets,
+                                     size_t n_sets, const sv_fe* points, size_t n_points,
+                                     const sv_fe* mu, const sv_fe* gamma, int form, void* stream,
+                                     sv_fe* d_work, uint64_t work_elems,
+                                     sv_g1_jacobian* out_w_partial) SV_NOEXCEPT;
+int sv_bn254_shplonk_witness_device(uint64_t handle, size_t offset, const sv_shplonk_set* sets,
+                                    size_t n_sets, const sv_fe* points, size_t n_points,
+                                    const uint64_t* set_lens, const sv_fe* gamma,
+                                    const sv_fe* z_prime, int form, void* stream, const sv_fe* d_work,
+                                    uint64_t work_elems,
+                                    sv_g1_jacobian* out_w_prime_partial) SV_NOEXCEPT;
 
 /* ---- Poseidon sponge over BN254 Fr --------------------------
  * x^5 HADES permutation, width t = 3 (R_F 8, R_P 57, rate 2: the SDK's PoseidonTranscript,

@@ -1391,6 +1391,515 @@ int sv_bn254_kzg_open_batch_device(uint64_t handle, size_t offset, const sv_fe* 
   SV_GUARD_END
 }
 
+// ---- several points: the multi-point pass, division by several roots, the SHPLONK (bdfg21) opening ----
+namespace {
+// the checks on a table of polynomials, one function per status so that a call can put its own
+// rules of the same status beside them: null / alignment, then emptiness, then the lengths
+int polys_pointer_check(const sv_fe* const* d_polys, size_t m) {
+  const size_t seen = std::min<size_t>(m, SV_OPEN_BATCH_MAX);
+  for (size_t j = 0; j < seen; j++) {
+    if (!d_polys[j]) {
+      sv::set_error("null pointer (polynomial %zu)", j);
+      return SV_ERR_ARG;
+    }
+    if ((uintptr_t)d_polys[j] % 16) {
+      sv::set_error("polynomial %zu is not 16-byte aligned", j);
+      return SV_ERR_ARG;
+    }
+  }
+  return SV_OK;
+}
+int polys_empty_check(const uint64_t* lens, size_t m) {
+  if (m == 0) {
+    sv::set_error("batch should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  for (size_t j = 0; j < std::min<size_t>(m, SV_OPEN_BATCH_MAX); j++)
+    if (lens[j] == 0) {
+      sv::set_error("polynomial should not be empty (polynomial %zu)", j);
+      return SV_ERR_EMPTY;
+    }
+  return SV_OK;
+}
+int polys_length_check(const uint64_t* lens, size_t m, size_t* N) {
+  if (m > SV_OPEN_BATCH_MAX) {
+    sv::set_error("m = %zu exceeds the per-call limit of %d polynomials", m, SV_OPEN_BATCH_MAX);
+    return SV_ERR_LEN;
+  }
+  size_t longest = 0;
+  for (size_t j = 0; j < m; j++) {
+    if (lens[j] > kMaxSetRows) {
+      sv::set_error("n = %llu exceeds the per-device limit 2^26 (polynomial %zu)", (unsigned long long)lens[j], j);
+      return SV_ERR_LEN;
+    }
+    longest = std::max<size_t>(longest, lens[j]);
+  }
+  *N = longest;
+  return SV_OK;
+}
+int points_reduced_check(const sv_fe* points, size_t K, const char* what) {
+  for (size_t k = 0; k < K; k++)
+    if (!host::f_is_reduced(fe_in(points[k]), host::R64)) {
+      sv::set_error("%s %zu not reduced mod the scalar field order", what, k);
+      return SV_ERR_ARG;
+    }
+  return SV_OK;
+}
+int points_count_check(size_t K) {
+  if (K > SV_EVAL_POINTS_MAX) {
+    sv::set_error("K = %zu exceeds the per-call limit of %d points", K, SV_EVAL_POINTS_MAX);
+    return SV_ERR_LEN;
+  }
+  return SV_OK;
+}
+bool fe_same(const sv_fe& a, const sv_fe& b) { return memcmp(a.l, b.l, sizeof a.l) == 0; }
+sv_fe fe_mont(const sv_fe& a, int form) { return form == SV_MONTGOMERY ? a : poly_fr_to_mont(a); }
+}  // namespace
+
+int sv_bn254_fr_poly_eval_points_device(const sv_fe* const* d_polys, const uint64_t* lens, size_t m,
+                                        const sv_fe* points, size_t K, int form, int device, void* stream,
+                                        sv_fe* out_evals) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_polys || !lens || !points || !out_evals) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  SV_TRY(polys_pointer_check(d_polys, m));
+  SV_TRY(polys_empty_check(lens, m));
+  if (K == 0) {
+    sv::set_error("the points should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  SV_TRY(points_count_check(K));
+  size_t N = 0;
+  SV_TRY(polys_length_check(lens, m, &N));
+  SV_TRY(points_reduced_check(points, K, "point"));
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, (hipStream_t)stream);
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  // the table (the polynomials' rows, then the points' rows: one copy) and the pass's scratch
+  const size_t rb = batch_table_bytes(m), tb = rb + Workspace::aligned(K * kPointRowBytes);
+  const size_t hb = poly_points_head_bytes(m, K);
+  SV_TRY(ws->reserve(tb + Workspace::aligned(poly_points_scratch_bytes(m, K, N))));
+  SV_TRY(ws->reserve_pinned(tb + hb));
+  std::vector<sv_fe> ones(m, poly_fr_one());  // the rows' weights play no part in an evaluation
+  poly_batch_fill_table_weights(reinterpret_cast<BatchRow*>(ws->pinned), d_polys, lens, m, ones.data(), SV_MONTGOMERY);
+  poly_points_fill_rows(ws->pinned + rb, points, K, form, N);
+  char* d_scratch = ws->buf + tb;
+  SV_HIP(hipMemcpyAsync(ws->buf, ws->pinned, rb + K * kPointRowBytes, hipMemcpyHostToDevice, ws->stream));
+  SV_TRY(poly_eval_points_enqueue(reinterpret_cast<const BatchRow*>(ws->buf), m, N, ws->buf + rb, ws->pinned + rb, K,
+                                  form, d_scratch, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned + tb, d_scratch, hb, hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl.armed = false;
+  uint32_t errv;
+  memcpy(&errv, ws->pinned + tb + kPointsErrOffset, 4);
+  if (errv) {
+    sv::set_error("invalid input: coefficient not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  memcpy(out_evals, ws->pinned + tb + kPointsEvalsOffset, m * K * sizeof(sv_fe));
+  return SV_OK;
+  SV_GUARD_END
+}
+
+int sv_bn254_fr_poly_div_roots_device(const sv_fe* d_coeffs, size_t n, const sv_fe* roots, size_t K, int form,
+                                      int device, void* stream, sv_fe* d_quotient) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_coeffs || !roots || !d_quotient) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if ((uintptr_t)d_coeffs % 16 || (uintptr_t)d_quotient % 16) {
+    sv::set_error("d_coeffs or d_quotient is not 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (n == 0 || K == 0) {
+    sv::set_error(n == 0 ? "polynomial should not be empty" : "the roots should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  SV_TRY(points_count_check(K));
+  if (n > kMaxSetRows) {
+    sv::set_error("n = %zu exceeds the per-device limit 2^26", n);
+    return SV_ERR_LEN;
+  }
+  SV_TRY(points_reduced_check(roots, K, "root"));
+  if (n <= K) {
+    sv::set_error("n = %zu coefficients leave no quotient by %zu roots", n, K);
+    return SV_ERR_ARG;
+  }
+  const uintptr_t cb = (uintptr_t)d_coeffs, qb = (uintptr_t)d_quotient;
+  if (qb < cb + n * sizeof(sv_fe) && cb < qb + (n - K) * sizeof(sv_fe)) {
+    sv::set_error("d_quotient overlaps d_coeffs (phase 3 reads the coefficients again while it writes)");
+    return SV_ERR_ARG;
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, (hipStream_t)stream);
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  const size_t tbytes = K > 1 ? Workspace::aligned((n - 1) * sizeof(sv_fe)) : 0;  // the quotients in between
+  SV_TRY(ws->reserve_in(2 * tbytes + 1));
+  SV_TRY(ws->reserve(poly_div_roots_scratch_bytes(n, K)));
+  SV_TRY(ws->reserve_pinned(kDivHeadBytes));
+  void* const tmp[2] = {ws->inbuf, ws->inbuf + tbytes};
+  SV_TRY(poly_div_roots_enqueue(d_coeffs, n, roots, K, form, form, d_quotient, tmp, ws->buf, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned, ws->buf, kDivHeadBytes, hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl.armed = false;
+  sv_fe unused;
+  return div_result(ws->pinned, &unused);
+  SV_GUARD_END
+}
+
+// ---- SHPLONK (bdfg21): W over h = sum_i gamma^i h_i, then W' over the linearisation's quotient ----
+namespace {
+// What both calls derive from the sets: N = the longest set, the rows of h, and per set N_i, K_i.
+struct ShplonkShape {
+  size_t N = 0, h_len = 0;
+  std::vector<size_t> set_len;  // N_i
+};
+
+// The checks both calls share on sets and points, in the header's order.  `set_lens` are the N_i
+// (the witness call's argument; the quotient call passes what it derived from lens).
+int shplonk_set_pointer_rules(const sv_shplonk_set* sets, size_t n_sets, const sv_fe* points, size_t n_points) {
+  if (n_sets == 0 || n_points == 0) {
+    sv::set_error(n_sets == 0 ? "the sets should not be empty" : "the points should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  for (size_t i = 0; i < std::min<size_t>(n_sets, SV_OPEN_BATCH_MAX); i++)
+    if (sets[i].num_polys == 0 || sets[i].num_points == 0) {
+      sv::set_error("set %zu should not be empty", i);
+      return SV_ERR_EMPTY;
+    }
+  (void)points;
+  return SV_OK;
+}
+int shplonk_set_length_rules(const sv_shplonk_set* sets, size_t n_sets) {
+  if (n_sets > SV_OPEN_BATCH_MAX) {
+    sv::set_error("n_sets = %zu exceeds the per-call limit of %d", n_sets, SV_OPEN_BATCH_MAX);
+    return SV_ERR_LEN;
+  }
+  for (size_t i = 0; i < n_sets; i++) SV_TRY(points_count_check(sets[i].num_points));
+  return SV_OK;
+}
+// the sets partition [0, m) and [0, n_points) in order; no point twice inside a set
+int shplonk_partition_rules(const sv_shplonk_set* sets, size_t n_sets, size_t m, const sv_fe* points,
+                            size_t n_points) {
+  uint64_t poly = 0, point = 0;
+  for (size_t i = 0; i < n_sets; i++) {
+    if (sets[i].first_poly != poly || sets[i].first_point != point) {
+      sv::set_error("the sets do not partition the arrays (set %zu starts at polynomial %u, point %u)", i,
+                    sets[i].first_poly, sets[i].first_point);
+      return SV_ERR_ARG;
+    }
+    poly += sets[i].num_polys, point += sets[i].num_points;
+  }
+  if (poly != m || point != n_points) {
+    sv::set_error("the sets do not partition the arrays (%llu polynomials of %zu, %llu points of %zu)",
+                  (unsigned long long)poly, m, (unsigned long long)point, n_points);
+    return SV_ERR_ARG;
+  }
+  for (size_t i = 0; i < n_sets; i++) {
+    const sv_fe* p = points + sets[i].first_point;
+    for (uint32_t a = 0; a < sets[i].num_points; a++)
+      for (uint32_t b = a + 1; b < sets[i].num_points; b++)
+        if (fe_same(p[a], p[b])) {
+          sv::set_error("repeated point in set %zu (points %u and %u)", i, a, b);
+          return SV_ERR_ARG;
+        }
+  }
+  return SV_OK;
+}
+void shplonk_shape(const sv_shplonk_set* sets, size_t n_sets, ShplonkShape* s) {
+  s->N = s->h_len = 0;
+  for (size_t i = 0; i < n_sets; i++) {
+    s->N = std::max(s->N, s->set_len[i]);
+    if (s->set_len[i] > sets[i].num_points) s->h_len = std::max(s->h_len, s->set_len[i] - sets[i].num_points);
+  }
+}
+int shplonk_work_rules(size_t n_sets, size_t N, const void* d_work, uint64_t work_elems) {
+  if ((uint64_t)(n_sets + 1) * N > work_elems) {
+    sv::set_error("work_elems = %llu is too small: %zu sets of up to %zu coefficients need %llu",
+                  (unsigned long long)work_elems, n_sets, N, (unsigned long long)(n_sets + 1) * N);
+    return SV_ERR_ARG;
+  }
+  (void)d_work;
+  return SV_OK;
+}
+int shplonk_handle_rules(uint64_t handle, size_t offset, size_t rows, BaseSet* t) {
+  if (!set_lookup(handle, t)) return SV_ERR_ARG;
+  if (offset > t->n || rows > t->n - offset) {
+    sv::set_error("rows [%zu, %zu + %zu) reach past base set %llu (%zu rows)", offset, offset, rows,
+                  (unsigned long long)handle, t->n);
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+// one pass's flag, copied behind the kernels into its own 32-byte slot of the pinned staging
+int shplonk_flag_copy(Workspace* ws, size_t pinned_at, const void* d_scratch) {
+  SV_HIP(hipMemcpyAsync(ws->pinned + pinned_at, static_cast<const char*>(d_scratch) + kBatchErrOffset, 4,
+                        hipMemcpyDeviceToHost, ws->stream));
+  return SV_OK;
+}
+bool shplonk_any_flag(const Workspace* ws, size_t pinned_at, size_t count) {
+  for (size_t i = 0; i < count; i++) {
+    uint32_t errv;
+    memcpy(&errv, ws->pinned + pinned_at + 32 * i, 4);
+    if (errv) return true;
+  }
+  return false;
+}
+const sv_fe kFeZero = {{0, 0, 0, 0}};
+}  // namespace
+
+int sv_bn254_shplonk_work_elems(size_t n_sets, size_t N, uint64_t* elems) noexcept {
+  SV_GUARD_BEGIN
+  if (!elems) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (n_sets == 0 || N == 0) {
+    sv::set_error("the sets should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (n_sets > SV_OPEN_BATCH_MAX || N > kMaxSetRows) {
+    sv::set_error("n_sets = %zu, N = %zu out of range", n_sets, N);
+    return SV_ERR_LEN;
+  }
+  *elems = (uint64_t)(n_sets + 1) * N;  // c_1 .. c_s, then h, N elements apart
+  return SV_OK;
+  SV_GUARD_END
+}
+
+int sv_bn254_shplonk_quotient_device(uint64_t handle, size_t offset, const sv_fe* const* d_polys, const uint64_t* lens,
+                                     size_t m, const sv_shplonk_set* sets, size_t n_sets, const sv_fe* points,
+                                     size_t n_points, const sv_fe* mu, const sv_fe* gamma, int form, void* stream,
+                                     sv_fe* d_work, uint64_t work_elems, sv_g1_jacobian* out_w_partial) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_polys || !lens || !sets || !points || !mu || !gamma || !d_work || !out_w_partial) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  SV_TRY(polys_pointer_check(d_polys, m));
+  if ((uintptr_t)d_work % 16) {
+    sv::set_error("d_work is not 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  SV_TRY(polys_empty_check(lens, m));
+  SV_TRY(shplonk_set_pointer_rules(sets, n_sets, points, n_points));
+  size_t longest = 0;
+  SV_TRY(polys_length_check(lens, m, &longest));
+  SV_TRY(shplonk_set_length_rules(sets, n_sets));
+  SV_TRY(points_reduced_check(points, std::min<size_t>(n_points, (size_t)SV_OPEN_BATCH_MAX * SV_EVAL_POINTS_MAX), "point"));
+  SV_TRY(points_reduced_check(mu, 1, "mu"));
+  SV_TRY(points_reduced_check(gamma, 1, "gamma"));
+  SV_TRY(shplonk_partition_rules(sets, n_sets, m, points, n_points));
+  ShplonkShape sh;
+  sh.set_len.assign(n_sets, 0);
+  for (size_t i = 0; i < n_sets; i++)
+    for (uint32_t j = 0; j < sets[i].num_polys; j++)
+      sh.set_len[i] = std::max<size_t>(sh.set_len[i], lens[sets[i].first_poly + j]);
+  shplonk_shape(sets, n_sets, &sh);
+  const size_t N = sh.N;
+  SV_TRY(shplonk_work_rules(n_sets, N, d_work, work_elems));
+  for (size_t j = 0; j < m; j++) {  // the combinations are written while other blocks still read the polynomials
+    const uintptr_t pb = (uintptr_t)d_polys[j], wb = (uintptr_t)d_work;
+    if (wb < pb + lens[j] * sizeof(sv_fe) && pb < wb + (n_sets + 1) * N * sizeof(sv_fe)) {
+      sv::set_error("d_work overlaps polynomial %zu", j);
+      return SV_ERR_ARG;
+    }
+  }
+  BaseSet t;
+  SV_TRY(shplonk_handle_rules(handle, offset, sh.h_len, &t));
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(t.dev, (hipStream_t)stream);
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+
+  // The sets whose combination is longer than their number of points have a quotient h_i; the
+  // others' is zero.  Device: the table (the m polynomials' rows with the powers of mu per set, then
+  // one row per h_i with gamma^i), one pass's scratch per set and one for h's, the divisions'.
+  // Input buffer: the h_i, N rows apart, then the two quotients in between.  Pinned: the table, then
+  // one flag slot per pass.
+  std::vector<size_t> live;
+  for (size_t i = 0; i < n_sets; i++)
+    if (sh.set_len[i] > sets[i].num_points) live.push_back(i);
+  const size_t slot = Workspace::aligned(N * sizeof(sv_fe));
+  const size_t tb = batch_table_bytes(m + n_sets);
+  std::vector<size_t> scratch_at(n_sets + 1);
+  size_t at = tb;
+  for (size_t i = 0; i < n_sets; i++) {
+    scratch_at[i] = at;
+    at += Workspace::aligned(poly_batch_scratch_bytes(sets[i].num_polys, sh.set_len[i]));
+  }
+  scratch_at[n_sets] = at;
+  at += Workspace::aligned(poly_batch_scratch_bytes(std::max<size_t>(live.size(), 1), std::max<size_t>(sh.h_len, 1)));
+  const size_t div_at = at;
+  at += Workspace::aligned(poly_div_roots_scratch_bytes(N, 2));
+  SV_TRY(ws->reserve(at));
+  SV_TRY(ws->reserve_in((n_sets + 2) * slot + 1));
+  SV_TRY(ws->reserve_pinned(tb + 32 * (n_sets + 1)));
+  memset(ws->pinned + tb, 0, 32 * (n_sets + 1));
+  BatchRow* rows = reinterpret_cast<BatchRow*>(ws->pinned);
+  for (size_t i = 0; i < n_sets; i++)
+    poly_batch_fill_table(rows + sets[i].first_poly, d_polys + sets[i].first_poly, lens + sets[i].first_poly,
+                          sets[i].num_polys, *mu, form);
+  {
+    const sv_fe g = fe_mont(*gamma, form);
+    sv_fe gp = poly_fr_one();
+    size_t r = 0;
+    for (size_t i = 0; i < n_sets; i++) {
+      if (r < live.size() && live[r] == i) {
+        rows[m + r].coeffs = ws->inbuf + i * slot;
+        rows[m + r].len = sh.set_len[i] - sets[i].num_points;
+        rows[m + r].vpow = gp;
+        r++;
+      }
+      gp = poly_fr_mul(gp, g);
+    }
+  }
+  const BatchRow* d_table = reinterpret_cast<const BatchRow*>(ws->buf);
+  SV_HIP(hipMemcpyAsync(ws->buf, rows, (m + live.size()) * sizeof(BatchRow), hipMemcpyHostToDevice, ws->stream));
+  void* const tmp[2] = {ws->inbuf + n_sets * slot, ws->inbuf + (n_sets + 1) * slot};
+  for (size_t i = 0; i < n_sets; i++) {
+    sv_fe* c = d_work + i * N;
+    SV_TRY(poly_combine_eval_enqueue(d_table + sets[i].first_poly, sets[i].num_polys, sh.set_len[i], kFeZero, form,
+                                     SV_MONTGOMERY, c, ws->buf + scratch_at[i], ws->stream));
+    SV_TRY(shplonk_flag_copy(ws, tb + 32 * i, ws->buf + scratch_at[i]));
+    if (sh.set_len[i] <= sets[i].num_points) continue;
+    sv_fe roots[SV_EVAL_POINTS_MAX];
+    for (uint32_t k = 0; k < sets[i].num_points; k++) roots[k] = fe_mont(points[sets[i].first_point + k], form);
+    SV_TRY(poly_div_roots_enqueue(c, sh.set_len[i], roots, sets[i].num_points, SV_MONTGOMERY, SV_MONTGOMERY,
+                                  ws->inbuf + i * slot, tmp, ws->buf + div_at, ws->stream));
+  }
+  Xyzz w = host::x_identity();
+  if (sh.h_len > 0) {  // the MSM synchronises the stream, so the flags have landed when it returns
+    sv_fe* h = d_work + n_sets * N;
+    SV_TRY(poly_combine_eval_enqueue(d_table + m, live.size(), sh.h_len, kFeZero, SV_MONTGOMERY, SV_MONTGOMERY, h,
+                                     ws->buf + scratch_at[n_sets], ws->stream));
+    const MsmResident set{t.rows, t.vtab, t.n, offset};
+    SV_TRY(msm_run_resident_device(set, h, sh.h_len, SV_MONTGOMERY, t.dev, ws->stream, &w));
+  } else {
+    SV_HIP(hipStreamSynchronize(ws->stream));
+  }
+  dl.armed = false;
+  if (shplonk_any_flag(ws, tb, n_sets)) {
+    sv::set_error("invalid input: coefficient not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  jacobian_out(w, out_w_partial);
+  return SV_OK;
+  SV_GUARD_END
+}
+
+int sv_bn254_shplonk_witness_device(uint64_t handle, size_t offset, const sv_shplonk_set* sets, size_t n_sets,
+                                    const sv_fe* points, size_t n_points, const uint64_t* set_lens,
+                                    const sv_fe* gamma, const sv_fe* z_prime, int form, void* stream,
+                                    const sv_fe* d_work, uint64_t work_elems,
+                                    sv_g1_jacobian* out_w_prime_partial) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!sets || !points || !set_lens || !gamma || !z_prime || !d_work || !out_w_prime_partial) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if ((uintptr_t)d_work % 16) {
+    sv::set_error("d_work is not 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  SV_TRY(shplonk_set_pointer_rules(sets, n_sets, points, n_points));
+  for (size_t i = 0; i < std::min<size_t>(n_sets, SV_OPEN_BATCH_MAX); i++)
+    if (set_lens[i] == 0) {
+      sv::set_error("polynomial should not be empty (set %zu)", i);
+      return SV_ERR_EMPTY;
+    }
+  SV_TRY(shplonk_set_length_rules(sets, n_sets));
+  for (size_t i = 0; i < n_sets; i++)
+    if (set_lens[i] > kMaxSetRows) {
+      sv::set_error("n = %llu exceeds the per-device limit 2^26 (set %zu)", (unsigned long long)set_lens[i], i);
+      return SV_ERR_LEN;
+    }
+  SV_TRY(points_reduced_check(points, std::min<size_t>(n_points, (size_t)SV_OPEN_BATCH_MAX * SV_EVAL_POINTS_MAX), "point"));
+  SV_TRY(points_reduced_check(gamma, 1, "gamma"));
+  SV_TRY(points_reduced_check(z_prime, 1, "z_prime"));
+  uint64_t polys = 0;
+  for (size_t i = 0; i < n_sets; i++) polys += sets[i].num_polys;
+  SV_TRY(shplonk_partition_rules(sets, n_sets, polys, points, n_points));
+  for (size_t k = 0; k < n_points; k++)
+    if (fe_same(points[k], *z_prime)) {
+      sv::set_error("z_prime equals point %zu", k);
+      return SV_ERR_ARG;
+    }
+  ShplonkShape sh;
+  sh.set_len.assign(set_lens, set_lens + n_sets);
+  shplonk_shape(sets, n_sets, &sh);
+  const size_t N = sh.N;
+  SV_TRY(shplonk_work_rules(n_sets, N, d_work, work_elems));
+  BaseSet t;
+  SV_TRY(shplonk_handle_rules(handle, offset, N - 1, &t));
+  if (N == 1) {  // L is a constant: no quotient term, no MSM
+    jacobian_out(host::x_identity(), out_w_prime_partial);
+    return SV_OK;
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(t.dev, (hipStream_t)stream);
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  // L = sum_i gamma^i Z_1(z') / Z_i(z') c_i - Z_1(z') h: one weighted pass over the rows of d_work,
+  // then the single opening's division by (X - z') and the set's MSM
+  const size_t n_rows = n_sets + (sh.h_len > 0 ? 1 : 0);
+  std::vector<sv_fe> weights(n_rows);
+  std::vector<const sv_fe*> ptrs(n_rows);
+  std::vector<uint64_t> rlens(n_rows);
+  const sv_fe zp = fe_mont(*z_prime, form), g = fe_mont(*gamma, form);
+  sv_fe z1 = poly_fr_one(), gp = poly_fr_one();
+  for (size_t i = 0; i < n_sets; i++) {
+    sv_fe zi = poly_fr_one();
+    for (uint32_t k = 0; k < sets[i].num_points; k++)
+      zi = poly_fr_mul(zi, poly_fr_sub(zp, fe_mont(points[sets[i].first_point + k], form)));
+    if (i == 0) z1 = zi;
+    weights[i] = poly_fr_mul(gp, poly_fr_mul(z1, poly_fr_inv(zi)));
+    ptrs[i] = d_work + i * N;
+    rlens[i] = sh.set_len[i];
+    gp = poly_fr_mul(gp, g);
+  }
+  if (sh.h_len > 0) {
+    weights[n_sets] = poly_fr_sub(kFeZero, z1);
+    ptrs[n_sets] = d_work + n_sets * N;
+    rlens[n_sets] = sh.h_len;
+  }
+  const size_t tb = batch_table_bytes(n_rows);
+  const size_t bbytes = tb + Workspace::aligned(poly_batch_scratch_bytes(n_rows, N));
+  const size_t lbytes = Workspace::aligned(N * sizeof(sv_fe));
+  SV_TRY(ws->reserve_in(lbytes + Workspace::aligned((N - 1) * sizeof(sv_fe) + 1)));
+  SV_TRY(ws->reserve(bbytes + Workspace::aligned(poly_div_scratch_bytes(N))));
+  SV_TRY(ws->reserve_pinned(tb + 32));
+  BatchRow* rows = reinterpret_cast<BatchRow*>(ws->pinned);
+  poly_batch_fill_table_weights(rows, ptrs.data(), rlens.data(), n_rows, weights.data(), SV_MONTGOMERY);
+  SV_HIP(hipMemcpyAsync(ws->buf, rows, n_rows * sizeof(BatchRow), hipMemcpyHostToDevice, ws->stream));
+  void* d_l = ws->inbuf;
+  void* d_quot = ws->inbuf + lbytes;
+  SV_TRY(poly_combine_eval_enqueue(reinterpret_cast<const BatchRow*>(ws->buf), n_rows, N, kFeZero, SV_MONTGOMERY,
+                                   SV_MONTGOMERY, d_l, ws->buf + tb, ws->stream));
+  SV_TRY(shplonk_flag_copy(ws, tb, ws->buf + tb));
+  SV_TRY(poly_div_linear_enqueue(d_l, N, zp, SV_MONTGOMERY, SV_MONTGOMERY, d_quot, ws->buf + bbytes, ws->stream));
+  Xyzz w = host::x_identity();
+  const MsmResident set{t.rows, t.vtab, t.n, offset};
+  SV_TRY(msm_run_resident_device(set, d_quot, N - 1, SV_MONTGOMERY, t.dev, ws->stream, &w));
+  dl.armed = false;
+  if (shplonk_any_flag(ws, tb, 1)) {
+    sv::set_error("invalid input: the work buffer holds an element not below r");
+    return SV_ERR_ARG;
+  }
+  jacobian_out(w, out_w_prime_partial);
+  return SV_OK;
+  SV_GUARD_END
+}
+
 int sv_bn254_poseidon_permute(sv_fe* states, size_t n, int t, int form) noexcept {
   SV_GUARD_BEGIN
   SV_TRY(check_form(form));

@@ -11,7 +11,8 @@ All compute runs in libsvgpu.so (HIP, gfx950); there is no CPU fallback.
 """
 from ._lib import (SV_CANONICAL, SV_MONTGOMERY, ArgumentError, DeviceError, EmptyError, LengthError,
                    OutOfMemoryError, SvError, lib)
-from .kzg import AssertionFailure, KzgAccumulator, KzgAs, KzgDecidingKey, gwc19_open, gwc19_query_sets
+from .kzg import (AssertionFailure, Bdfg21Opening, KzgAccumulator, KzgAs, KzgDecidingKey, bdfg21_open,
+                  bdfg21_query_sets, gwc19_open, gwc19_query_sets)
 from .loader import (BaseTable, NativeLoader, ReferencePanic, ResidentBases, batch_multi_scalar_multiplication,
                      fold_partials, msm_arrays, make_refs, msm_batch_arrays, msm_refs, multi_scalar_multiplication)
 from .poseidon import Poseidon, PoseidonTranscript
@@ -33,6 +34,18 @@ def poly_combine_eval_device(polys, z, v, **kwargs):
     """svgpu.device.poly_combine_eval_device (imported on first use: that module needs torch)."""
     from .device import poly_combine_eval_device as run
     return run(polys, z, v, **kwargs)
+
+
+def poly_eval_points_device(polys, points, **kwargs):
+    """svgpu.device.poly_eval_points_device (imported on first use: that module needs torch)."""
+    from .device import poly_eval_points_device as run
+    return run(polys, points, **kwargs)
+
+
+def poly_div_roots_device(coeffs, roots, **kwargs):
+    """svgpu.device.poly_div_roots_device (imported on first use: that module needs torch)."""
+    from .device import poly_div_roots_device as run
+    return run(coeffs, roots, **kwargs)
 
 
 def version() -> str:

@@ -19,6 +19,7 @@ SV_MONTGOMERY = 1
 SV_OK, SV_ERR_EMPTY, SV_ERR_LEN, SV_ERR_ARG, SV_ERR_DEVICE, SV_ERR_OOM = range(6)
 
 SV_OPEN_BATCH_MAX = 4096  # polynomials per batched opening
+SV_EVAL_POINTS_MAX = 16   # points per evaluation call, roots per division, points per SHPLONK set
 
 SV_ENC_HALO2_COMPRESSED = 0
 SV_ENC_EVM = 1
@@ -73,6 +74,11 @@ class sv_g2_affine(Structure):
 
 class sv_fq12(Structure):
     _fields_ = [("c", sv_fq2 * 6)]
+
+
+class sv_shplonk_set(Structure):
+    _fields_ = [("first_poly", c_uint32), ("num_polys", c_uint32), ("first_point", c_uint32),
+                ("num_points", c_uint32)]
 
 
 class sv_msm_stats(Structure):
@@ -130,6 +136,17 @@ PROTOTYPES = [
                                                       c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("sv_bn254_kzg_open_batch_device", c_int, [c_uint64, c_size_t, c_void_p, c_void_p, c_size_t, POINTER(sv_fe),
                                                 POINTER(sv_fe), c_int, c_void_p, c_void_p, POINTER(sv_g1_jacobian)]),
+    ("sv_bn254_fr_poly_eval_points_device", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int,
+                                                     c_void_p, c_void_p]),
+    ("sv_bn254_fr_poly_div_roots_device", c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int, c_void_p,
+                                                   c_void_p]),
+    ("sv_bn254_shplonk_work_elems", c_int, [c_size_t, c_size_t, POINTER(c_uint64)]),
+    ("sv_bn254_shplonk_quotient_device", c_int, [c_uint64, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                                  c_void_p, c_size_t, POINTER(sv_fe), POINTER(sv_fe), c_int, c_void_p,
+                                                  c_void_p, c_uint64, POINTER(sv_g1_jacobian)]),
+    ("sv_bn254_shplonk_witness_device", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                 POINTER(sv_fe), POINTER(sv_fe), c_int, c_void_p, c_void_p, c_uint64,
+                                                 POINTER(sv_g1_jacobian)]),
     ("sv_bn254_poseidon_permute", c_int, [c_void_p, c_size_t, c_int, c_int]),
     ("sv_bn254_poseidon_permute_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_squeeze", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

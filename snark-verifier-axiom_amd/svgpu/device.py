@@ -149,6 +149,54 @@ def poly_combine_eval_device(polys, z: int, v: int, form: int = _lib.SV_MONTGOME
     return evals, (out[:n] if combined else None)
 
 
+def fe_array(values, form: int):
+    """A host array of sv_fe (at least one element) holding the canonical ints `values` in `form`."""
+    arr = (_lib.sv_fe * max(len(values), 1))()
+    for k, x in enumerate(values):
+        arr[k] = enc.fr_struct(x, form)
+    return arr
+
+
+def eval_points_pointers(ptrs, lens, m: int, points, form: int, device: int, stream) -> List[List[int]]:
+    """sv_bn254_fr_poly_eval_points_device over raw host arrays of device pointers and lengths ->
+    [[p_j(x_k) for k] for j] as canonical ints."""
+    K = len(points)
+    ev = (_lib.sv_fe * max(m * K, 1))()
+    _lib.check(_lib.lib.sv_bn254_fr_poly_eval_points_device(ptrs, lens, m, fe_array(points, form), K, form, device,
+                                                            stream, ev),
+               "sv_bn254_fr_poly_eval_points_device")
+    return [[enc.fr_from_struct(ev[j * K + k], form) for k in range(K)] for j in range(m)]
+
+
+def poly_eval_points_device(polys, points, form: int = _lib.SV_MONTGOMERY) -> List[List[int]]:
+    """Every p_j(x_k) for the HBM-resident polynomials p_j ((n_j, 4) int64 limbs in `form`) and the
+    points x_k (canonical ints, at most SV_EVAL_POINTS_MAX; repeats allowed) in one pass that reads
+    each polynomial once -> [[p_j(x_k) for k] for j], canonical ints."""
+    keep, ptrs, lens = batch_tables(polys)
+    d, stream = (_dev_index(keep[0]), _stream_handle(keep[0].device)) if keep else (0, None)
+    return eval_points_pointers(ptrs, lens, len(keep), list(points), form, d, stream)
+
+
+def poly_div_roots_device(coeffs: torch.Tensor, roots, form: int = _lib.SV_MONTGOMERY,
+                          out: torch.Tensor = None) -> torch.Tensor:
+    """The quotient of p by prod_k (X - x_k), remainder dropped, for the HBM-resident coefficients of
+    p ((n, 4) int64 limbs in `form`) and the roots x_k (canonical ints, K < n) -> n - K rows in `form`.
+    `out` (at least n - K rows) must not overlap coeffs."""
+    d = _dev_index(coeffs)
+    coeffs = coeffs.contiguous()
+    roots = list(roots)
+    n, K = coeffs.shape[0], len(roots)
+    if out is None:
+        out = torch.empty((max(n - K, 1), 4), dtype=torch.int64, device=coeffs.device)
+    elif (out.device != coeffs.device or out.dtype != torch.int64 or not out.is_contiguous() or out.dim() != 2
+          or out.shape[1] != 4 or out.shape[0] < n - K):
+        raise _lib.LengthError(f"poly_div_roots: out must be a contiguous (>= {n - K}, 4) int64 tensor on {coeffs.device}")
+    _lib.check(_lib.lib.sv_bn254_fr_poly_div_roots_device(coeffs.data_ptr(), n, fe_array(roots, form), K, form, d,
+                                                          _stream_handle(coeffs.device), out.data_ptr()),
+               "sv_bn254_fr_poly_div_roots_device")
+    return out[:max(n - K, 0)]
+
+
 def last_msm_stats() -> dict:
     s = _lib.sv_msm_stats()
     _lib.check(_lib.lib.sv_msm_last_stats(ctypes.byref(s)), "sv_msm_last_stats")

@@ -165,6 +165,133 @@ def gwc19_query_sets(queries: Sequence[Tuple[int, int]]) -> list:
     return sets
 
 
+def bdfg21_query_sets(queries: Sequence[Tuple[int, int]]) -> list:
+    """The query sets of a SHPLONK opening, grouped as the reference's query_sets does
+    (snark-verifier/src/pcs/kzg/multiopen/bdfg21.rs:117-167): first every polynomial collects its
+    distinct shifts in query order (a repeated query is dropped), then polynomials group by the SET
+    of their shifts, in order of first appearance; a set keeps the shift order of its first
+    polynomial -> [([shift], [poly index], [[query index per shift of the set] per polynomial])]."""
+    poly_shifts: list = []
+    for qi, (poly, shift) in enumerate(queries):
+        for ps in poly_shifts:
+            if ps[0] == poly:
+                if shift not in ps[1]:
+                    ps[1].append(shift)
+                    ps[2].append(qi)
+                break
+        else:
+            poly_shifts.append((poly, [shift], [qi]))
+    sets: list = []
+    for poly, shifts, where in poly_shifts:
+        for s in sets:
+            if set(s[0]) == set(shifts):
+                s[1].append(poly)
+                s[2].append([where[shifts.index(x)] for x in s[0]])
+                break
+        else:
+            sets.append((shifts, [poly], [where]))
+    return sets
+
+
+class Bdfg21Opening:
+    """The prover's side of Bdfg21::verify (bdfg21.rs:47-79) on a resident base set, in the order a
+    transcript needs it: the evaluations on construction (`.evals`, one per query, in query order),
+    then W = `.quotient(mu, gamma)`, then W' = `.witness(z_prime)`.  `polys` are (n_j, 4) int64 torch
+    tensors in `form` in HBM on the set's device, `queries` a list of (poly index, shift), z a
+    canonical int; query (p, shift) opens polynomial p at shift * z.  The object owns the work
+    buffer that carries the combinations c_i and h from the first call to the second; the library
+    keeps nothing.  Two MSMs whatever the number of shifts."""
+
+    def __init__(self, rset, polys, queries: Sequence[Tuple[int, int]], z: int, offset: int = 0,
+                 form: int = _lib.SV_MONTGOMERY):
+        import torch
+        from . import device as dv
+        if rset.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        self.rset, self.offset, self.form = rset, offset, form
+        self.sets = bdfg21_query_sets(queries)
+        ordered = [polys[p] for _, members, _ in self.sets for p in members]
+        self._keep, self._ptrs, self._lens = dv.batch_tables(ordered)
+        self._stream = dv._stream_handle(self._keep[0].device) if self._keep else None
+        self.points, descr, self.set_lens = [], [], []
+        first_poly = 0
+        for shifts, members, _ in self.sets:
+            descr.append((first_poly, len(members), len(self.points), len(shifts)))
+            self.set_lens.append(max(self._keep[first_poly + j].shape[0] for j in range(len(members))))
+            self.points += [shift * z % enc.R for shift in shifts]
+            first_poly += len(members)
+        self._sets = (_lib.sv_shplonk_set * max(len(descr), 1))(*[_lib.sv_shplonk_set(*d) for d in descr])
+        self._points = dv.fe_array(self.points, form)
+        self._set_lens = (ctypes.c_uint64 * max(len(descr), 1))(*self.set_lens)
+        # the evaluations enter the transcript before mu exists: one multi-point pass per set
+        at = {}
+        for (shifts, members, _), (fp, np_, fk, nk) in zip(self.sets, descr):
+            sub_p = (ctypes.c_void_p * np_)(*[self._ptrs[fp + j] for j in range(np_)])
+            sub_l = (ctypes.c_uint64 * np_)(*[self._lens[fp + j] for j in range(np_)])
+            es = dv.eval_points_pointers(sub_p, sub_l, np_, self.points[fk:fk + nk], form, rset.device, self._stream)
+            for j, p in enumerate(members):
+                for k, shift in enumerate(shifts):
+                    at[(p, shift)] = es[j][k]
+        self.evals = [at[(p, shift)] for p, shift in queries]
+        elems = ctypes.c_uint64(0)
+        _lib.check(_lib.lib.sv_bn254_shplonk_work_elems(len(descr), max(self.set_lens, default=0), ctypes.byref(elems)),
+                   "sv_bn254_shplonk_work_elems")
+        self.work = torch.empty((elems.value, 4), dtype=torch.int64, device=f"cuda:{rset.device}")
+        self._gamma = None
+
+    def _affine(self, part):
+        out = _lib.sv_g1_affine()
+        _lib.check(_lib.lib.sv_bn254_g1_fold(ctypes.byref(part), 1, ctypes.byref(out), _lib.SV_CANONICAL),
+                   "sv_bn254_g1_fold")
+        return enc.g1_from_struct(out)
+
+    def quotient(self, mu: int, gamma: int):
+        """W = sum_k h_k set[offset + k] for h = sum_i gamma^i h_i (None = the identity)."""
+        if self.rset.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        ms, gs, part = enc.fr_struct(mu, self.form), enc.fr_struct(gamma, self.form), _lib.sv_g1_jacobian()
+        _lib.check(_lib.lib.sv_bn254_shplonk_quotient_device(
+            self.rset.handle, self.offset, self._ptrs, self._lens, len(self._keep), self._sets, len(self.sets),
+            self._points, len(self.points), ctypes.byref(ms), ctypes.byref(gs), self.form, self._stream,
+            self.work.data_ptr(), self.work.shape[0], ctypes.byref(part)), "sv_bn254_shplonk_quotient_device")
+        self._gamma = gamma
+        return self._affine(part)
+
+    def witness(self, z_prime: int):
+        """W' = the witness of the linearisation L at z' (None = the identity); after quotient()."""
+        if self.rset.handle is None:
+            raise _lib.ArgumentError("base set is closed")
+        if self._gamma is None:
+            raise _lib.ArgumentError("witness() needs the work buffer that quotient() fills")
+        gs, zs, part = enc.fr_struct(self._gamma, self.form), enc.fr_struct(z_prime, self.form), _lib.sv_g1_jacobian()
+        _lib.check(_lib.lib.sv_bn254_shplonk_witness_device(
+            self.rset.handle, self.offset, self._sets, len(self.sets), self._points, len(self.points),
+            self._set_lens, ctypes.byref(gs), ctypes.byref(zs), self.form, self._stream, self.work.data_ptr(),
+            self.work.shape[0], ctypes.byref(part)), "sv_bn254_shplonk_witness_device")
+        return self._affine(part)
+
+
+def bdfg21_open(rset, polys, queries: Sequence[Tuple[int, int]], z: int, challenges, offset: int = 0,
+                form: int = _lib.SV_MONTGOMERY) -> Tuple[list, Point, Point]:
+    """A SHPLONK opening on a resident base set -> (evaluations in query order, W, W').
+    `challenges` is (mu, gamma, z') as canonical ints, or a transcript, driven in the order of
+    Bdfg21Proof::read (bdfg21.rs:101-114): squeeze mu, squeeze gamma, absorb W, squeeze z', absorb W'
+    (the caller absorbs the evaluations before the call, as its protocol orders them)."""
+    op = Bdfg21Opening(rset, polys, queries, z, offset=offset, form=form)
+    if isinstance(challenges, (tuple, list)):
+        mu, gamma, z_prime = challenges
+        w = op.quotient(mu, gamma)
+        return op.evals, w, op.witness(z_prime)
+    mu = challenges.squeeze_challenge()
+    gamma = challenges.squeeze_challenge()
+    w = op.quotient(mu, gamma)
+    challenges.common_ec_point(w)
+    z_prime = challenges.squeeze_challenge()
+    w_prime = op.witness(z_prime)
+    challenges.common_ec_point(w_prime)
+    return op.evals, w, w_prime
+
+
 def gwc19_open(rset, polys, queries: Sequence[Tuple[int, int]], z: int, v: int, offset: int = 0,
                form: int = _lib.SV_MONTGOMERY) -> Tuple[list, list]:
     """The prover's side of Gwc19::verify (gwc19.rs:43-80) on a resident base set: `polys` are

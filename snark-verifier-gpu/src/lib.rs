@@ -76,6 +76,18 @@ pub struct SvMsmRef {
     pub scalar: *const SvFe,
     pub base: *const SvG1Affine,
 }
+/// One query set of a SHPLONK opening (bdfg21.rs:117-167): its polynomials and points as ranges of
+/// the call's arrays, which the sets partition in order.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct SvShplonkSet {
+    pub first_poly: u32,
+    pub num_polys: u32,
+    pub first_point: u32,
+    pub num_points: u32,
+}
+/// sv_shplonk_set's limit on the points of one set (and of one evaluation call).
+pub const SV_EVAL_POINTS_MAX: usize = 16;
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct SvMsmStats {
@@ -166,6 +178,24 @@ extern "C" {
                                           lens: *const u64, m: usize, z: *const SvFe, v: *const SvFe,
                                           form: c_int, stream: *mut c_void, out_evals: *mut SvFe,
                                           out_witness_partial: *mut SvG1Jacobian) -> c_int;
+    pub fn sv_bn254_fr_poly_eval_points_device(d_polys: *const *const SvFe, lens: *const u64, m: usize,
+                                               points: *const SvFe, k: usize, form: c_int, device: c_int,
+                                               stream: *mut c_void, out_evals: *mut SvFe) -> c_int;
+    pub fn sv_bn254_fr_poly_div_roots_device(d_coeffs: *const SvFe, n: usize, roots: *const SvFe, k: usize,
+                                             form: c_int, device: c_int, stream: *mut c_void,
+                                             d_quotient: *mut SvFe) -> c_int;
+    pub fn sv_bn254_shplonk_work_elems(n_sets: usize, n: usize, elems: *mut u64) -> c_int;
+    pub fn sv_bn254_shplonk_quotient_device(handle: u64, offset: usize, d_polys: *const *const SvFe,
+                                            lens: *const u64, m: usize, sets: *const SvShplonkSet, n_sets: usize,
+                                            points: *const SvFe, n_points: usize, mu: *const SvFe,
+                                            gamma: *const SvFe, form: c_int, stream: *mut c_void,
+                                            d_work: *mut SvFe, work_elems: u64,
+                                            out_w_partial: *mut SvG1Jacobian) -> c_int;
+    pub fn sv_bn254_shplonk_witness_device(handle: u64, offset: usize, sets: *const SvShplonkSet, n_sets: usize,
+                                           points: *const SvFe, n_points: usize, set_lens: *const u64,
+                                           gamma: *const SvFe, z_prime: *const SvFe, form: c_int,
+                                           stream: *mut c_void, d_work: *const SvFe, work_elems: u64,
+                                           out_w_prime_partial: *mut SvG1Jacobian) -> c_int;
     pub fn sv_bn254_poseidon_permute(states: *mut SvFe, n: usize, t: c_int, form: c_int) -> c_int;
     pub fn sv_bn254_poseidon_permute_device(d_states: *mut SvFe, n: usize, t: c_int, form: c_int, device: c_int,
                                             stream: *mut c_void) -> c_int;
@@ -556,6 +586,78 @@ impl ResidentBases {
         let rc = sv_bn254_g1_fold(&part, 1, &mut out, SV_MONTGOMERY);
         (rc == SV_OK).then(|| (evals, g1_out(out)))
     }
+
+    /// The first half of a SHPLONK opening (bdfg21.rs:47-79, the prover's side): W = Σ h_k · set[offset + k]
+    /// for h = Σ γ^i · h_i, h_i the quotient of c_i = Σ μ^j · p_ij by Π (X − z_ik).  `d_polys` in set
+    /// order, `sets` partitioning `d_polys` and `points`; `d_work` is the caller's device buffer of
+    /// `work_elems` elements (sv_bn254_shplonk_work_elems) that carries c_i and h to `shplonk_witness`.
+    ///
+    /// # Safety
+    /// Every `d_polys[j]` must point to `lens[j]` readable elements and `d_work` to `work_elems`
+    /// writable elements in device memory.
+    pub unsafe fn shplonk_quotient(&self, offset: usize, d_polys: &[*const Fr], lens: &[u64], sets: &[SvShplonkSet],
+                                   points: &[Fr], mu: &Fr, gamma: &Fr, stream: *mut c_void, d_work: *mut Fr,
+                                   work_elems: u64) -> Option<G1Affine> {
+        assert_eq!(d_polys.len(), lens.len());
+        let mut part = SvG1Jacobian::default();
+        let rc = sv_bn254_shplonk_quotient_device(self.handle, offset, d_polys.as_ptr() as *const *const SvFe,
+                                                  lens.as_ptr(), d_polys.len(), sets.as_ptr(), sets.len(),
+                                                  points.as_ptr() as *const SvFe, points.len(),
+                                                  mu as *const Fr as *const SvFe, gamma as *const Fr as *const SvFe,
+                                                  SV_MONTGOMERY, stream, d_work as *mut SvFe, work_elems, &mut part);
+        if rc != SV_OK {
+            return None;
+        }
+        let mut out = SvG1Affine::default();
+        let rc = sv_bn254_g1_fold(&part, 1, &mut out, SV_MONTGOMERY);
+        (rc == SV_OK).then(|| g1_out(out))
+    }
+
+    /// The second half: W' = the witness at z' of L = Σ γ^i · Z_1(z')/Z_i(z') · c_i − Z_1(z') · h, read
+    /// from the `d_work` that `shplonk_quotient` filled; `set_lens[i]` = the longest polynomial of set i.
+    ///
+    /// # Safety
+    /// `d_work` must point to `work_elems` readable elements in device memory.
+    pub unsafe fn shplonk_witness(&self, offset: usize, sets: &[SvShplonkSet], points: &[Fr], set_lens: &[u64],
+                                  gamma: &Fr, z_prime: &Fr, stream: *mut c_void, d_work: *const Fr,
+                                  work_elems: u64) -> Option<G1Affine> {
+        assert_eq!(sets.len(), set_lens.len());
+        let mut part = SvG1Jacobian::default();
+        let rc = sv_bn254_shplonk_witness_device(self.handle, offset, sets.as_ptr(), sets.len(),
+                                                 points.as_ptr() as *const SvFe, points.len(), set_lens.as_ptr(),
+                                                 gamma as *const Fr as *const SvFe,
+                                                 z_prime as *const Fr as *const SvFe, SV_MONTGOMERY, stream,
+                                                 d_work as *const SvFe, work_elems, &mut part);
+        if rc != SV_OK {
+            return None;
+        }
+        let mut out = SvG1Affine::default();
+        let rc = sv_bn254_g1_fold(&part, 1, &mut out, SV_MONTGOMERY);
+        (rc == SV_OK).then(|| g1_out(out))
+    }
+}
+
+/// Elements of the device work buffer of a SHPLONK opening over `n_sets` sets whose longest
+/// polynomial has `n` coefficients.
+pub fn shplonk_work_elems(n_sets: usize, n: usize) -> Option<u64> {
+    let mut elems = 0u64;
+    let rc = unsafe { sv_bn254_shplonk_work_elems(n_sets, n, &mut elems) };
+    (rc == SV_OK).then_some(elems)
+}
+
+/// Every p_j(x_k) for polynomials in device memory in one pass that reads each polynomial once:
+/// `[j * points.len() + k]`.
+///
+/// # Safety
+/// Every `d_polys[j]` must point to `lens[j]` readable Montgomery elements on `device`.
+pub unsafe fn poly_eval_points_device(d_polys: &[*const Fr], lens: &[u64], points: &[Fr], device: c_int,
+                                      stream: *mut c_void) -> Option<Vec<Fr>> {
+    assert_eq!(d_polys.len(), lens.len());
+    let mut evals = vec![Fr::zero(); d_polys.len() * points.len()];
+    let rc = sv_bn254_fr_poly_eval_points_device(d_polys.as_ptr() as *const *const SvFe, lens.as_ptr(), d_polys.len(),
+                                                 points.as_ptr() as *const SvFe, points.len(), SV_MONTGOMERY, device,
+                                                 stream, evals.as_mut_ptr() as *mut SvFe);
+    (rc == SV_OK).then_some(evals)
 }
 
 impl Drop for ResidentBases {
