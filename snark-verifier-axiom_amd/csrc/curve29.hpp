@@ -10,6 +10,10 @@
 //          and leaves X, Y, ZZZ as they were), so every reader tests ZZ alone.  A non-identity
 //          state never has ZZ = 0 mod p, since ZZ3 = ZZ PP and PP != 0 mod p;
 //   point  x2, y2 below 2p (R' form), never the identity (callers skip it).
+//   A product's output is below a b / R' + (1 + 2^-28) p (field29.hpp's lazy reduction steps); the
+//   sums below leave that margin (the tightest, Y3: 64 p^2 / R' = 0.38p).  X3 = Rd^2 / R' - PPP - 2Q
+//   + 6p is below 7.3p, inside the 8p the state allows, and PPP below 1.2p: the chain's Y3 reads
+//   Q - X3 + 8p and 2p - PPP as redundant limbs (sub_lazy), which needs those two margins.
 // The formulas are madd-2008-s / mdbl-2008-s, as xyzz_madd_2p / xyzz_mdbl in curve.hpp.
 #pragma once
 #include "field29.hpp"
@@ -93,7 +97,10 @@ SV29_HD Xyzz madd_live(const Xyzz& p, const F& x2, const F& y2, bool neg, int& s
   const F PP = sqr(Pd), PPP = mul(Pd, PP), Q = mul(p.X, PP);  // < 2p
   // X3 = Rd^2 - PPP - 2Q + 6p in the square's high columns: in (0, 8p)
   const F X3 = sqr_sub2c<6>(Rd, PPP, Q);
-  const F Y3 = mul_sum2(Rd, sub<8>(Q, X3), p.Y, sub<2>(zero(), PPP));
+  // Y3 = Rd (Q - X3 + 8p) + Y (2p - PPP), one reduction, below 2p as in madd.  The two differences
+  // feed only this product, so they stay redundant limbs (sub_lazy: no carry pass).  Its top-limb
+  // rule holds: X3 < Rd^2 / R' + p + 6p < 7.3p (Rd < 6p) and PPP < Pd PP / R' + p < 1.2p (Pd < 10p)
+  const F Y3 = mul_sum2(Rd, sub_lazy<8>(Q, X3), p.Y, sub_lazy<2>(zero(), PPP));
   return {X3, Y3, mul(p.ZZ, PP), mul(p.ZZZ, PPP)};
 }
 // 2 (x2, +-y2) as a chain state (madd_live's special == 2): dbl-2008-s-1 at Z = 1 -- the same
@@ -106,7 +113,7 @@ SV29_HD Xyzz dbl_start(const F& x2, const F& y2, bool neg) {
   const F Rd = add(add(x2s, x2s), x2s);   // < 6p
   const F PP = sqr(Pd), PPP = mul(Pd, PP), Q = mul(x2, PP);
   const F X3 = sqr_sub2c<6>(Rd, zero(), Q);
-  const F Y3 = mul_sum2(Rd, sub<8>(Q, X3), ys, sub<2>(zero(), PPP));
+  const F Y3 = mul_sum2(Rd, sub_lazy<8>(Q, X3), ys, sub_lazy<2>(zero(), PPP));  // as madd_live's
   return {X3, Y3, PP, PPP};
 }
 

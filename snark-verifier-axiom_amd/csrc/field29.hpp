@@ -14,6 +14,7 @@
 // value * R' mod p with R' = 2^261, little-endian limbs v[0..8], each in
 // [0, 2^29) ("normalized"); values are LAZILY reduced -- each operation states the bound of its
 // output, always below 2^261.
+//   (a product's reduction adds below (1 + 2^-28) p to a b / R': SV29_REDUCE_COLUMN)
 //   mul / sqr:   inputs below 12p  -> output below 2p   (12^2 p^2 / R' + p < 2p: 144 p < R' = 169.6 p)
 //   mul_sum2:    inputs below  9p  -> output below 2p   (2 * 81 p^2 / R' + p < 2p)
 //   mul_sum3:    a_i below 9p, b_i below p -> output below 2p (3 * 9 p^2 / R' + p < 2p; a column
@@ -38,9 +39,15 @@ namespace r29 {
 constexpr int L = 9;
 constexpr uint32_t MASK = (1u << 29) - 1;
 
-// the moduli: k * modulus as normalized 29-bit limbs (k = 0..8) and -modulus^-1 mod 2^29
+// the moduli: k * modulus as normalized 29-bit limbs (k = 0..8), -modulus^-1 mod 2^29, and
+// 2^-29 mod the modulus as normalized limbs (ri: the reduction's lazy steps)
 struct FqM29 {  // p
   static constexpr uint32_t NP = 0x4866389u;
+  SV29_HD static constexpr uint32_t ri(int i) {
+    constexpr uint32_t C[9] = {0x17789a9fu, 0x5ffc3dcu,  0xd6bde42u, 0x1cf152e3u, 0x18eb055fu,
+                               0xed815e2u,  0x16626d2u, 0xb8bab0fu, 0x6d7c4u};
+    return C[i];
+  }
   SV29_HD static constexpr uint32_t kp(int k, int i) {
     constexpr uint32_t T[9][9] = {
         {0, 0, 0, 0, 0, 0, 0, 0, 0},
@@ -57,6 +64,11 @@ struct FqM29 {  // p
 };
 struct FrM29 {  // r
   static constexpr uint32_t NP = 0xfffffffu;
+  SV29_HD static constexpr uint32_t ri(int i) {
+    constexpr uint32_t C[9] = {0x18f05361u, 0x12bb1feu,  0xf5d8135u,  0x1e6275f6u, 0x7e7a880u,
+                               0x10c6bf1fu, 0x11f74a6cu, 0x6fdaecbu, 0x183227u};
+    return C[i];
+  }
   SV29_HD static constexpr uint32_t kp(int k, int i) {
     constexpr uint32_t T[9][9] = {
         {0, 0, 0, 0, 0, 0, 0, 0, 0},
@@ -121,20 +133,37 @@ SV29_HD void to_words(const F29<M>& a, uint32_t* w) {  // a below 2^256
 SV29_HD uint64_t mad(uint32_t a, uint32_t b, uint64_t c) { return (uint64_t)a * b + c; }  // v_mad_u64_u32
 
 // Montgomery reduction tail shared by the products: column k's sum in acc (products of the inputs
-// already added), m_i p_{k-i} for i < k added here; the low 9 columns fix m_k, the high ones give t.
-#define SV29_REDUCE_COLUMN(k)                                          \
-  {                                                                    \
-    _Pragma("unroll") for (int i = 0; i < L; i++) {                    \
-      const int j = (k) - i;                                           \
-      if (i < (k) && j >= 1 && j < L) acc = mad(m[i], M::kp(1, j), acc); \
-    }                                                                  \
-    if ((k) < L) {                                                     \
-      m[(k)] = ((uint32_t)acc * M::NP) & MASK;                         \
-      acc = mad(m[(k)], M::kp(1, 0), acc);                             \
-    } else {                                                           \
-      t.v[(k) - L] = (uint32_t)acc & MASK;                             \
-    }                                                                  \
-    acc >>= 29;                                                        \
+// already added), the earlier steps' products added here; the low 9 columns each clear their limb,
+// the high ones give t.
+// Steps 0 .. LZ - 1 are LAZY: the column's low limb c is dropped and c (2^-29 mod p) 2^(29 (k + 1))
+// added instead -- the same value mod p, nine mads into columns k + 1 .. k + 9 as a standard step's,
+// but c is the limb as it stands: no c NP multiply on the column's dependent chain (7 of a product's
+// 9).  Steps LZ .. 8 are standard (m = c NP mod 2^29, m p added).  What the steps add to the result:
+// lazy step k at most 2^29 p 2^(29 (k + 1) - 261) = p 2^(29 (k - 7)), all seven below p 2^-28; the two
+// standard ones (m_7 2^203 + m_8 2^232) p / R' < p.  So t < a b / R' + (1 + 2^-28) p, and every
+// "below 2p" in this file keeps its margin (the tightest, mul_sum2: 162 / 169.6 + 1 + 2^-28 < 2).
+// Step 7 has to stay standard: lazy, it alone would add up to p.  A column still collects at most
+// nine reduction products below 2^58.
+constexpr int LZ = L - 2;
+#define SV29_REDUCE_COLUMN(k)                                              \
+  {                                                                        \
+    _Pragma("unroll") for (int i = 0; i < L; i++) {                        \
+      const int j = i < LZ ? (k) - 1 - i : (k) - i;                        \
+      if (i < LZ) {                                                        \
+        if (i < (k) && j >= 0 && j < L) acc = mad(m[i], M::ri(j), acc);    \
+      } else {                                                             \
+        if (i < (k) && j >= 1 && j < L) acc = mad(m[i], M::kp(1, j), acc); \
+      }                                                                    \
+    }                                                                      \
+    if ((k) < LZ) {                                                        \
+      m[(k)] = (uint32_t)acc & MASK;                                       \
+    } else if ((k) < L) {                                                  \
+      m[(k)] = ((uint32_t)acc * M::NP) & MASK;                             \
+      acc = mad(m[(k)], M::kp(1, 0), acc);                                 \
+    } else {                                                               \
+      t.v[(k) - L] = (uint32_t)acc & MASK;                                 \
+    }                                                                      \
+    acc >>= 29;                                                            \
   }
 
 // a b / R' mod p, below 2p for a, b below 12p
@@ -179,7 +208,12 @@ SV29_HD F29<M> sqr(const F29<M>& a) {
 }
 
 // (a0 b0 + a1 b1) / R' mod p with ONE reduction, below 2p for inputs below 9p (a column: at most
-// 27 products below 2^58 plus the carry, below 2^63)
+// 27 products below 2^58 plus the carry, below 2^63).
+// b0 and b1 may be sub_lazy's redundant limbs (values below 10p and 2p, limbs below 3 * 2^29 and
+// 2^30) against normalized a0, a1: a column then holds 9 products below 3 * 2^58, 9 below 2 * 2^58,
+// the reduction's 9 below 2^58 and the carry: below 54 * 2^58 + 2^35 < 2^64 in the unsigned
+// accumulator.  The product only reads limbs, so the value and the output bound are those of the
+// normalized operands.
 template <class M>
 SV29_HD F29<M> mul_sum2(const F29<M>& a0, const F29<M>& b0, const F29<M>& a1, const F29<M>& b1) {
   uint32_t m[L];
@@ -335,6 +369,22 @@ SV29_HD F29<M> sub(const F29<M>& a, const F29<M>& b) {
     c = x >> 29;  // arithmetic: floor division by 2^29 (-1, 0 or 1)
     r.v[i] = (uint32_t)x & MASK;
   }
+  return r;
+}
+
+// a - b + K p as REDUNDANT limbs, for a result that only feeds a product (mul_sum2's b0 / b1): one
+// subtraction and one constant per limb, no carry pass (sub's add, arithmetic shift and mask).
+// K p is spread as c_i = K p_i + 2^29 [i < 8] - [i > 0], which sums to exactly K p (each borrowed
+// 2^29 is returned by the next limb's - 1), so limb i = a_i + c_i - b_i lies in [0, 3 * 2^29) for
+// i < 8: c_i >= 2^29 - 1 >= b_i.  The top limb borrows nothing: it is a_8 + K p_8 - 1 - b_8, which
+// needs b_8 < K p_8, so the caller keeps b below (K - 1/2) p (p / 2^233 is about 1.6e6).  The value
+// is exactly a - b + K p; the limbs are not normalized, so nothing but a product may read them.
+template <int K, class M>
+SV29_HD F29<M> sub_lazy(const F29<M>& a, const F29<M>& b) {
+  F29<M> r;
+#pragma unroll
+  for (int i = 0; i < L; i++)
+    r.v[i] = a.v[i] + (M::kp(K, i) + (i < L - 1 ? 1u << 29 : 0u) - (i > 0 ? 1u : 0u)) - b.v[i];
   return r;
 }
 

@@ -369,6 +369,10 @@ __global__ void k_glv_phix(const G1Aff* __restrict__ bases, uint32_t n, uint4* _
 // are checked to be reduced (Montgomery input is used as is).
 static constexpr int kPhiVtab = 2;  // k_bin_hist's phi64 value for "phix is the r29 table"
 static constexpr int kVtabRec = 9;  // uint2 per record
+// The identity's record carries this bit in y's top limb, which a point never sets (y below 2p keeps
+// that limb below 2^23), and is otherwise zero: k_accumulate, the table's only reader, tests the one
+// limb instead of OR-ing all eighteen for every entry, and reads nothing else of such a record.
+static constexpr uint32_t kVtabIdentity = 0x80000000u;
 __device__ __forceinline__ void st_rec29(uint2* o, const r29::F& x, const r29::F& y) {
   o[0] = make_uint2(x.v[0], x.v[1]);
   o[1] = make_uint2(x.v[2], x.v[3]);
@@ -393,7 +397,10 @@ __device__ __forceinline__ void ld_rec29(const uint2* __restrict__ o, r29::F& x,
 __device__ __forceinline__ void vtab_put_pt(const G1Aff& a, uint32_t i, uint4* __restrict__ vtab, uint32_t nsplit,
                                             bool glv, uint32_t* __restrict__ err) {
   if (err && (!a.x.is_reduced() || !a.y.is_reduced())) atomicOr(err, 1u);
-  const r29::F y = r29::to_r29(a.y.v), x = r29::to_r29(a.x.v);  // below 2p
+  r29::F y = r29::to_r29(a.y.v);  // below 2p
+  const r29::F x = r29::to_r29(a.x.v);
+  // the identity (all-zero limbs), tested here once per point and marked for the per-entry reader
+  if (r29::is_zero(x) && r29::is_zero(y)) y.v[r29::L - 1] = kVtabIdentity;
   uint2* t = reinterpret_cast<uint2*>(vtab);
   st_rec29(t + kVtabRec * (size_t)i, x, y);
   if (glv) {  // beta x in the 29-bit form directly: beta R' (GLV_BETA_MONT re-expressed, 2^261)
@@ -1074,9 +1081,9 @@ __global__ void __launch_bounds__(kBlock, R29 ? SV_ACC29_MIN_BLOCKS : SV_ACC_MIN
         // the entry's point first: a segment starting here starts from it
         const uint32_t v = vnext;
         if (e + 1 < e_end) vnext = ent[e + 1];
-        r29::F x, y;  // the table's limbs (the identity: all-zero limbs)
+        r29::F x, y;  // the table's limbs (the identity: kVtabIdentity in y's top limb)
         ld_rec29(reinterpret_cast<const uint2*>(phix) + (size_t)kVtabRec * (v & 0x7fffffffu), x, y);
-        const bool live = !(r29::is_zero(x) && r29::is_zero(y)), neg = (v & 0x80000000u) != 0;
+        const bool live = (y.v[r29::L - 1] & kVtabIdentity) == 0, neg = (v & 0x80000000u) != 0;
         bool fresh = false;
         if (e >= ge || empty) {  // divergent: a segment ends here, or the chain is empty
           if (e >= ge) {  // segment [seg_start, ge) of bucket g ends inside this chunk
