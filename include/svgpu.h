@@ -21,7 +21,31 @@
  *    `form` says whether inputs/outputs are canonical (SV_CANONICAL) or Montgomery with
  *    R = 2^256 (SV_MONTGOMERY, zero-copy with halo2curves memory);
  *  - the affine identity is (0, 0), as halo2curves encodes it;
- *  - calls are re-entrant: each call draws a stream + workspace from a per-device pool.
+ *  - calls are re-entrant: each call draws a workspace (scratch, events, a stream of its own) from
+ *    a per-device pool.
+ *  - Streams.  Every `*_device` entry point takes `void* stream`, a hipStream_t of `device` (of the
+ *    handle's device where there is no `device` argument).  NULL means that device's legacy
+ *    default stream (hipStream_t 0, the stream PyTorch calls the default stream).
+ *    1. Ordered after the caller's stream: everything enqueued on `stream` before the call
+ *       happens-before every read and every write the call makes through its device pointers --
+ *       inputs that earlier work produces (read after write) and outputs that earlier work still
+ *       reads (write after read).  With a non-NULL stream the call's work runs on that stream.
+ *       With NULL it runs on the workspace's own non-blocking stream, made to wait for an event
+ *       recorded on the legacy default stream when the call starts (nothing is recorded when
+ *       that stream is found idle): the library never launches on the default stream itself, so
+ *       concurrent callers do not serialise against each other or against the device's blocking
+ *       streams.
+ *    2. Synchronous: every entry point except the two named in 3 returns with its outputs
+ *       complete, device outputs included ("synchronous on `stream`").  Given 1, all work
+ *       enqueued on `stream` before the call has then completed as well.
+ *    3. sv_bn254_poseidon_permute_device and sv_bn254_poseidon_squeeze_device are asynchronous:
+ *       their kernel is enqueued on `stream` itself (NULL: on the legacy default stream) and the
+ *       call returns at once.  The results are ordered for later work on the same stream; the
+ *       host reads them after synchronising that stream.
+ *    4. Not supported: stream capture (hipStreamBeginCapture / graphs: the calls synchronise), and
+ *       a `stream` that belongs to another device than the call's.
+ *    The host-buffer entry points take no stream: they read and write host memory only and are
+ *    synchronous.
  *  - there is NO CPU fallback inside this library: without a usable GPU every compute entry
  *    point returns SV_ERR_DEVICE (the Rust shim then keeps the reference's own CPU code path).
  */

@@ -358,7 +358,7 @@ int sv_bn254_g1_msm_device(const sv_g1_affine* d_bases, const sv_fe* d_scalars, 
   SV_TRY(check_form(form));
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
   Xyzz r;
-  SV_TRY(msm_run_device(d_bases, d_scalars, n, form, device, (hipStream_t)stream, &r));
+  SV_TRY(msm_run_device(d_bases, d_scalars, n, form, device, caller_stream(stream), &r));
   jacobian_out(r, out_partial);
   return SV_OK;
   SV_GUARD_END
@@ -440,7 +440,7 @@ int sv_bn254_kzg_decide_device(const sv_g2_affine* g2, const sv_g2_affine* s_g2,
     return SV_ERR_ARG;
   }
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  return decide_run_device(g2, s_g2, d_lhs, d_rhs, n, form, device, (hipStream_t)stream, first_fail,
+  return decide_run_device(g2, s_g2, d_lhs, d_rhs, n, form, device, caller_stream(stream), first_fail,
                            verdicts, gt);
   SV_GUARD_END
 }
@@ -674,7 +674,7 @@ int sv_bn254_g1_msm_batch_device(const sv_g1_affine* d_bases, const sv_fe* d_sca
   if (!d_bases || !d_scalars || !d_offsets || !d_out) return SV_ERR_ARG;
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
   SV_HIP(hipSetDevice(device));
-  return msm_batch_device(d_bases, d_scalars, d_offsets, nullptr, count, max_terms, form, device, (hipStream_t)stream,
+  return msm_batch_device(d_bases, d_scalars, d_offsets, nullptr, count, max_terms, form, device, caller_stream(stream),
                           d_out);
   SV_GUARD_END
 }
@@ -848,7 +848,7 @@ int sv_bn254_g1_msm_batch_table_device(uint64_t handle, const uint32_t* d_base_i
   }
   SV_HIP(hipSetDevice(t.dev));
   return msm_batch_fixed_device(t.pre, t.n, d_base_idx, d_scalars, d_offsets, count, form, t.dev,
-                                (hipStream_t)stream, d_out);
+                                caller_stream(stream), d_out);
   SV_GUARD_END
 }
 
@@ -880,7 +880,7 @@ int sv_bn254_g1_msm_batch_indexed_device(const sv_g1_affine* d_table, size_t tab
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
   SV_HIP(hipSetDevice(device));
   return msm_batch_device(d_table, d_scalars, d_offsets, nullptr, count, max_terms, form, device,
-                          (hipStream_t)stream, d_out, d_base_idx, table_len, table_form);
+                          caller_stream(stream), d_out, d_base_idx, table_len, table_form);
   SV_GUARD_END
 }
 
@@ -1001,7 +1001,7 @@ int sv_bn254_g1_bases_create_device(const sv_g1_affine* d_bases, size_t n, int f
                                     uint64_t* handle) noexcept {
   SV_GUARD_BEGIN
   SV_TRY(set_create_args(d_bases, n, form, handle));
-  return set_create(d_bases, true, n, form, device, (hipStream_t)stream, handle);
+  return set_create(d_bases, true, n, form, device, caller_stream(stream), handle);
   SV_GUARD_END
 }
 
@@ -1078,7 +1078,7 @@ int sv_bn254_g1_msm_bases_device(uint64_t handle, size_t offset, const sv_fe* d_
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
   const MsmResident set{t.rows, t.vtab, t.n, offset};
   Xyzz r;
-  SV_TRY(msm_run_resident_device(set, d_scalars, n, form, t.dev, (hipStream_t)stream, &r));
+  SV_TRY(msm_run_resident_device(set, d_scalars, n, form, t.dev, caller_stream(stream), &r));
   jacobian_out(r, out_partial);
   return SV_OK;
   SV_GUARD_END
@@ -1188,7 +1188,7 @@ int sv_bn254_fr_poly_div_linear_device(const sv_fe* d_coeffs, size_t n, const sv
     return SV_ERR_ARG;
   }
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  DrainedLease dl(device, (hipStream_t)stream);
+  DrainedLease dl(device, caller_stream(stream));
   if (!dl.lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = dl.ws();
   SV_TRY(ws->reserve(poly_div_scratch_bytes(n)));
@@ -1219,7 +1219,7 @@ int sv_bn254_kzg_open_device(uint64_t handle, size_t offset, const sv_fe* d_coef
   BaseSet t;
   SV_TRY(open_call_args(handle, offset, d_coeffs, n, z, form, out_eval, out_witness_partial, &t));
   Xyzz w;
-  SV_TRY(open_run(t, offset, d_coeffs, true, n, z, form, (hipStream_t)stream, out_eval, &w));
+  SV_TRY(open_run(t, offset, d_coeffs, true, n, z, form, caller_stream(stream), out_eval, &w));
   jacobian_out(w, out_witness_partial);
   return SV_OK;
   SV_GUARD_END
@@ -1338,7 +1338,7 @@ int sv_bn254_fr_poly_combine_eval_device(const sv_fe* const* d_polys, const uint
     }
   }
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  DrainedLease dl(device, (hipStream_t)stream);
+  DrainedLease dl(device, caller_stream(stream));
   if (!dl.lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = dl.ws();
   SV_TRY(ws->reserve(batch_device_bytes(m, N)));
@@ -1363,7 +1363,7 @@ int sv_bn254_kzg_open_batch_device(uint64_t handle, size_t offset, const sv_fe* 
     return SV_ERR_ARG;
   }
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  DrainedLease dl(t.dev, (hipStream_t)stream);
+  DrainedLease dl(t.dev, caller_stream(stream));
   if (!dl.lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = dl.ws();
   // pooled scratch: the table and the pass's totals, then the division's; c and q side by side in
@@ -1476,7 +1476,7 @@ int sv_bn254_fr_poly_eval_points_device(const sv_fe* const* d_polys, const uint6
   SV_TRY(polys_length_check(lens, m, &N));
   SV_TRY(points_reduced_check(points, K, "point"));
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  DrainedLease dl(device, (hipStream_t)stream);
+  DrainedLease dl(device, caller_stream(stream));
   if (!dl.lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = dl.ws();
   // the table (the polynomials' rows, then the points' rows: one copy) and the pass's scratch
@@ -1537,7 +1537,7 @@ int sv_bn254_fr_poly_div_roots_device(const sv_fe* d_coeffs, size_t n, const sv_
     return SV_ERR_ARG;
   }
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  DrainedLease dl(device, (hipStream_t)stream);
+  DrainedLease dl(device, caller_stream(stream));
   if (!dl.lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = dl.ws();
   const size_t tbytes = K > 1 ? Workspace::aligned((n - 1) * sizeof(sv_fe)) : 0;  // the quotients in between
@@ -1716,7 +1716,7 @@ int sv_bn254_shplonk_quotient_device(uint64_t handle, size_t offset, const sv_fe
   BaseSet t;
   SV_TRY(shplonk_handle_rules(handle, offset, sh.h_len, &t));
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  DrainedLease dl(t.dev, (hipStream_t)stream);
+  DrainedLease dl(t.dev, caller_stream(stream));
   if (!dl.lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = dl.ws();
 
@@ -1846,7 +1846,7 @@ int sv_bn254_shplonk_witness_device(uint64_t handle, size_t offset, const sv_shp
     return SV_OK;
   }
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  DrainedLease dl(t.dev, (hipStream_t)stream);
+  DrainedLease dl(t.dev, caller_stream(stream));
   if (!dl.lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = dl.ws();
   // L = sum_i gamma^i Z_1(z') / Z_i(z') c_i - Z_1(z') h: one weighted pass over the rows of d_work,
@@ -2017,7 +2017,7 @@ int sv_bn254_g1_decode_device(const uint8_t* d_data, size_t n, int encoding, int
   SV_HIP(hipSetDevice(device));
   int64_t fi = -1;
   SV_TRY(g1_decode_device(d_data, n, encoding, encoding == SV_ENC_EVM ? 64 : 32, 0, form, device,
-                          (hipStream_t)stream, d_out, &fi));
+                          caller_stream(stream), d_out, &fi));
   if (first_invalid) *first_invalid = fi;
   if (fi >= 0) {
     sv::set_error("Invalid elliptic curve point encoding in proof (point %lld)", (long long)fi);
@@ -2128,7 +2128,7 @@ int sv_gen_scalars_device(sv_fe* d_scalars, size_t n, uint64_t seed, uint64_t st
   SV_GUARD_BEGIN
   SV_TRY(check_form(form));
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  return gen_scalars_device(d_scalars, n, seed, start, form, device, (hipStream_t)stream);
+  return gen_scalars_device(d_scalars, n, seed, start, form, device, caller_stream(stream));
   SV_GUARD_END
 }
 
@@ -2137,7 +2137,7 @@ int sv_gen_bases_device(sv_g1_affine* d_bases, size_t n, uint64_t seed, uint64_t
   SV_GUARD_BEGIN
   SV_TRY(check_form(form));
   if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
-  return gen_bases_device(d_bases, n, seed, start, form, device, (hipStream_t)stream);
+  return gen_bases_device(d_bases, n, seed, start, form, device, caller_stream(stream));
   SV_GUARD_END
 }
 

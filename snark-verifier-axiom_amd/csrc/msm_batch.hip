@@ -1065,8 +1065,8 @@ static int msm_batch_small_host(const void* d_bases, const void* d_scalars, cons
   // on the caller's stream (no null-stream implicit sync); this route is synchronous for the host
   // anyway (msm_batch_windows_host waited for the window sums), so wait for the copy of `h`
   SV_HIP(hipSetDevice(device));
-  SV_HIP(hipMemcpyAsync(d_out, h.data(), h.size() * 8, hipMemcpyHostToDevice, stream));
-  SV_HIP(hipStreamSynchronize(stream));
+  SV_HIP(hipMemcpyAsync(d_out, h.data(), h.size() * 8, hipMemcpyHostToDevice, raw_stream(stream)));
+  SV_HIP(hipStreamSynchronize(raw_stream(stream)));
   return SV_OK;
 }
 

@@ -283,6 +283,35 @@ WsLease::WsLease(int device, hipStream_t user_stream) {
         ws_ = nullptr;
         return;
       }
+    if (hipEventCreateWithFlags(&ws_->order_ev, hipEventDisableTiming) != hipSuccess) {
+      set_error("hipEventCreate failed on device %d", device);
+      delete ws_;
+      ws_ = nullptr;
+      return;
+    }
+  }
+  if (user_stream == kCallerDefaultStream) {
+    // Ordered after the caller's (legacy default) stream without running on it: own_stream is
+    // non-blocking, so nothing but this event ties it to the work the caller enqueued there.
+    // Every call drains own_stream before it returns the lease, so the event is never re-recorded
+    // while a wait on it is outstanding.
+    //
+    // An idle default stream has nothing to wait for: the query alone (everything enqueued there
+    // has completed) orders the call, and a verifier's loop of synchronous calls pays no event
+    // record and no barrier in front of its first kernel (the decider's 0.52 ms call measured
+    // +0.011 ms with an unconditional record + wait).
+    const hipError_t busy = hipStreamQuery(nullptr);
+    if (busy == hipErrorNotReady) (void)hipGetLastError();  // not an error: keep it from the next launch check
+    if ((busy != hipSuccess && busy != hipErrorNotReady) ||
+        (busy == hipErrorNotReady && (hipEventRecord(ws_->order_ev, nullptr) != hipSuccess ||
+                                      hipStreamWaitEvent(ws_->own_stream, ws_->order_ev, 0) != hipSuccess))) {
+      set_error("ordering after the default stream failed on device %d", device);
+      std::lock_guard<std::mutex> lk(pool->mu);
+      pool->free_list.push_back(ws_);
+      ws_ = nullptr;
+      return;
+    }
+    user_stream = nullptr;
   }
   ws_->stream = user_stream ? user_stream : ws_->own_stream;
 }

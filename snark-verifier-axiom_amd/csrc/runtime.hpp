@@ -38,6 +38,7 @@ struct Workspace {
   hipStream_t sort_stream = nullptr;  // host-fed MSM: piece k + 1's sort beside piece k's accumulate
   static constexpr int kEvents = 64;
   hipEvent_t ev[kEvents] = {};
+  hipEvent_t order_ev = nullptr;  // recorded on the legacy default stream when a lease is ordered after it
 
 
   // carve `bytes` from the device buffer (256-B aligned); call reserve() first
@@ -65,7 +66,19 @@ struct Workspace {
   Helper* helper = nullptr;  // wait for the compute and copy streams (before freeing or reusing staging)
 };
 
-// RAII lease of a per-device workspace; stream override optional.
+// What a `*_device` entry point passes down for a NULL `stream` argument: the caller means the
+// device's legacy default stream.  The library never launches there (it would serialise every
+// concurrent caller against all blocking streams); a lease given this value runs on the
+// workspace's own stream, ordered after what the default stream holds at that moment.  Only
+// WsLease and raw_stream() interpret it; it never reaches a HIP call.
+static const hipStream_t kCallerDefaultStream = hipStreamLegacy;
+// the stream to hand to HIP for work that runs on the caller's stream itself
+inline hipStream_t raw_stream(hipStream_t s) { return s == kCallerDefaultStream ? nullptr : s; }
+inline hipStream_t caller_stream(void* s) { return s ? (hipStream_t)s : kCallerDefaultStream; }
+
+// RAII lease of a per-device workspace.  user_stream: a caller's stream (the call's work runs on
+// it), kCallerDefaultStream (own stream, made to wait for the legacy default stream), or nullptr
+// (own stream, unordered: the host-buffer entry points, whose inputs no stream produces).
 class WsLease {
  public:
   WsLease(int device, hipStream_t user_stream);

@@ -200,7 +200,12 @@ class Bdfg21Opening:
     tensors in `form` in HBM on the set's device, `queries` a list of (poly index, shift), z a
     canonical int; query (p, shift) opens polynomial p at shift * z.  The object owns the work
     buffer that carries the combinations c_i and h from the first call to the second; the library
-    keeps nothing.  Two MSMs whatever the number of shifts."""
+    keeps nothing.  Two MSMs whatever the number of shifts.
+
+    Streams: nothing is captured at construction.  The constructor's evaluation passes,
+    `quotient` and `witness` each run on the stream that is current (torch.cuda.current_stream) on
+    the polynomials' device when that call is made, like every other device call of this package;
+    each is synchronous, so the three may be made under different streams."""
 
     def __init__(self, rset, polys, queries: Sequence[Tuple[int, int]], z: int, offset: int = 0,
                  form: int = _lib.SV_MONTGOMERY):
@@ -212,7 +217,6 @@ class Bdfg21Opening:
         self.sets = bdfg21_query_sets(queries)
         ordered = [polys[p] for _, members, _ in self.sets for p in members]
         self._keep, self._ptrs, self._lens = dv.batch_tables(ordered)
-        self._stream = dv._stream_handle(self._keep[0].device) if self._keep else None
         self.points, descr, self.set_lens = [], [], []
         first_poly = 0
         for shifts, members, _ in self.sets:
@@ -238,6 +242,12 @@ class Bdfg21Opening:
                    "sv_bn254_shplonk_work_elems")
         self.work = torch.empty((elems.value, 4), dtype=torch.int64, device=f"cuda:{rset.device}")
         self._gamma = None
+
+    @property
+    def _stream(self):
+        """The current stream of the polynomials' device, read per call."""
+        from . import device as dv
+        return dv._stream_handle(self._keep[0].device) if self._keep else None
 
     def _affine(self, part):
         out = _lib.sv_g1_affine()
