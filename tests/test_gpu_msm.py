@@ -13,6 +13,22 @@ def _to_pt(row):
     return b.g1_from_bytes(np.asarray(row, dtype=np.uint64).tobytes())
 
 
+def _last_route():
+    """How the last single MSM on this thread ran, from sv_msm_last_stats: "small" (run_small zeroes
+    the statistics before msm_batch_windows_host, which never writes them), else the pipeline,
+    "glv" with ceil(128 / c) windows or "plain" with ceil(255 / c).  Only for calls with
+    num_gpus=1 or device inputs: they run on the calling thread, whose statistics these are."""
+    from svgpu import device as dv
+    s = dv.last_msm_stats()
+    c, w = s["window_bits"], s["num_windows"]
+    if c == 0 and w == 0:
+        return "small"
+    assert 4 <= c <= 16, s
+    routes = {-(-128 // c): "glv", -(-255 // c): "plain"}
+    assert w in routes, s
+    return routes[w]
+
+
 def _golden_inputs(c, oracle_cpp):
     from svgpu import encoding as enc
     if "scalars" in c:
@@ -142,7 +158,7 @@ def test_adversarial_single_bucket(gpu, oracle_cpp):
     assert svgpu.msm_arrays(B, S) == _to_pt(oracle_cpp.msm_pippenger(B, S, 0))
 
 
-def test_repeated_and_cancelling_points(gpu, oracle_cpp):
+def test_repeated_and_cancelling_points(gpu, oracle_cpp, monkeypatch):
     import svgpu
     n = 3000
     B = oracle_cpp.gen_bases(b.SEED_BASES, 10)
@@ -158,6 +174,16 @@ def test_repeated_and_cancelling_points(gpu, oracle_cpp):
     allp = enc.bases_array(pts + negs)
     sc = np.concatenate([S[:10], S[:10]])
     assert svgpu.msm_arrays(allp, sc) is None
+    # 20 terms take the small route (k_batch_uwin); the pipeline must give the identity too, without
+    # the GLV split (unset: off below 2^14 points) and with it (40 virtual points, 8 buckets a window)
+    monkeypatch.setenv("SVGPU_SMALL_MSM", "0")
+    for glv, route in ((None, "plain"), ("1", "glv")):
+        if glv is None:
+            monkeypatch.delenv("SVGPU_GLV", raising=False)
+        else:
+            monkeypatch.setenv("SVGPU_GLV", glv)
+        assert svgpu.msm_arrays(allp, sc, num_gpus=1) is None, route
+        assert _last_route() == route
 
 
 def test_invalid_scalar_rejected(gpu):
@@ -254,10 +280,21 @@ def test_edge_scalars(gpu, oracle_cpp, glv, monkeypatch):
     S = enc.scalars_array(ks)
     exp = _to_pt(oracle_cpp.msm_pippenger(B, S, 0))
     assert svgpu.msm_arrays(B, S, svgpu.SV_CANONICAL) == exp
-    # each edge scalar alone (single-term MSMs) -- the split of every k is exercised in isolation
+    # each edge scalar alone (single-term MSMs): at most 256 terms take the small route (k_batch_uwin),
+    # whatever SVGPU_GLV says, so this checks the small route's digits of every k, not the split
     for k in ks[:19]:
         Sk = enc.scalars_array([k])
         assert svgpu.msm_arrays(B[:1], Sk) == _to_pt(oracle_cpp.msm_pippenger(B[:1], Sk, 0)), hex(k)
+    assert svgpu.msm_arrays(B[:1], Sk, num_gpus=1) == _to_pt(oracle_cpp.msm_pippenger(B[:1], Sk, 0))
+    assert _last_route() == "small"
+    # the pipeline's split of every k in isolation: (k, 0) over two bases is the smallest MSM that
+    # msm_plan gives the split to (n >= 2; 4 virtual points), and the zero scalar adds nothing.
+    # k = 0 is the identity out of the pipeline.
+    monkeypatch.setenv("SVGPU_SMALL_MSM", "0")
+    for k in ks[:19]:
+        Sk = enc.scalars_array([k, 0])
+        assert svgpu.msm_arrays(B[:2], Sk, num_gpus=1) == _to_pt(oracle_cpp.msm_pippenger(B[:2], Sk, 0)), hex(k)
+        assert _last_route() == ("glv" if glv == "1" else "plain"), hex(k)
 
 
 @pytest.mark.parametrize("glv", ["0", "1"])
@@ -278,6 +315,16 @@ def test_glv_split_on_off(gpu, oracle_cpp, n, glv, monkeypatch):
         Bm = enc.bases_array(pts, svgpu.SV_MONTGOMERY)
         Sm = enc.scalars_array(sc, svgpu.SV_MONTGOMERY)
         assert svgpu.msm_arrays(Bm, Sm, svgpu.SV_MONTGOMERY) == exp
+    if n <= 256:
+        # the runs above took the small route (at most 256 terms), which has no split: the pipeline
+        # itself at 4, 6 and 130 virtual points, far fewer than the buckets of a window
+        assert svgpu.msm_arrays(B, S, svgpu.SV_CANONICAL, num_gpus=1) == exp
+        assert _last_route() == "small"
+        monkeypatch.setenv("SVGPU_SMALL_MSM", "0")
+        assert svgpu.msm_arrays(B, S, svgpu.SV_CANONICAL, num_gpus=1) == exp
+        assert _last_route() == ("glv" if glv == "1" else "plain")
+        assert svgpu.msm_arrays(Bm, Sm, svgpu.SV_MONTGOMERY, num_gpus=1) == exp
+        assert _last_route() == ("glv" if glv == "1" else "plain")
 
 
 @pytest.mark.parametrize("phi64", ["0", "1"])
@@ -293,6 +340,10 @@ def test_glv_phi_table_layouts(gpu, oracle_cpp, n, phi64, monkeypatch):
     B[n // 2] = 0  # identity (0, 0) maps to itself under phi
     exp = _to_pt(oracle_cpp.msm_pippenger(B, S, 0))
     assert svgpu.msm_arrays(B, S, svgpu.SV_CANONICAL) == exp
+    if n <= 256:  # the small route has no phi table: the pipeline's, at 6 virtual points
+        monkeypatch.setenv("SVGPU_SMALL_MSM", "0")
+        assert svgpu.msm_arrays(B, S, svgpu.SV_CANONICAL, num_gpus=1) == exp
+        assert _last_route() == "glv"
 
 
 @pytest.mark.parametrize("path", ["tree", "bucket_tree", "quad", "plain"])
