@@ -51,7 +51,12 @@ def test_montgomery_form(gpu, oracle_cpp, monkeypatch):
 
 
 def test_edge_suite_per_msm(gpu):
-    """zero scalars, identity bases, P and -P, repeated base, r - 1, 2^k, all-equal scalars."""
+    """zero scalars, identity bases, P and -P, repeated base, r - 1, 2^k, all-equal scalars.
+    8 MSMs through the host API: k_batch_uwin plus the host Horner, and no other route.  The same 8
+    MSMs (tests/degenerate_cases.py::edge_msms) run through every other row of the msm_batch.hip
+    table of tests/COVERAGE.md -- k_batch_fused, k_batch_buckets_q + k_batch_horner_b,
+    k_batch_windows_q, k_msm_batch_windows<5 / 8> with both Horners, the indexed entry point -- in
+    tests/test_gpu_msm_batch_degenerate.py; k_msm_batch_fixed has its own edge cases there."""
     import svgpu
     P = b.g1_mul(b.G1_GEN, 987654321)
     Q = b.g1_mul(b.G1_GEN, 5)
