@@ -387,6 +387,45 @@ int sv_bn254_shplonk_witness_device(uint64_t handle, size_t offset, const sv_shp
                                     uint64_t work_elems,
                                     sv_g1_jacobian* out_w_prime_partial) SV_NOEXCEPT;
 
+/* ---- Fr NTT on the device: forward, inverse and coset transforms ---------------------------
+ * A halo2 prover holds its columns as evaluations over the 2^k domain and computes its quotient on
+ * a coset of an extended domain; the openings above take coefficients.  This block is the change
+ * of basis for data that is already in HBM.
+ * fr_root_of_unity (host only, no GPU needed): omega_k = the reference's root_of_unity(k)
+ *   (snark-verifier/src/util/arithmetic.rs:89-96) = halo2curves' Fr::ROOT_OF_UNITY =
+ *   7^((r - 1) / 2^28) squared 28 - k times, in `form`; omega_0 = 1, omega_1 = r - 1; log_n > 28 is
+ *   SV_ERR_ARG.
+ * fr_ntt_device: with n = 2^log_n, omega = omega_log_n and g = *shift (a host pointer; NULL = 1),
+ *   SV_NTT_FORWARD  out[j] = sum_{i<n} in[i] (g omega^j)^i
+ *   SV_NTT_INVERSE  the exact inverse of the forward transform with the same g:
+ *                   out[i] = g^-i n^-1 sum_{j<n} in[j] omega^(-i j)
+ *   in natural order on both sides.  g = 1 forward is coefficients -> evaluations on the halo2
+ *   domain; g != 1 is the coset form of the extended-domain quotient.  `count` transforms lie back to
+ *   back: transform t occupies elements [t n, (t + 1) n) of d_in and of d_out (HBM on `device`).
+ *   d_out == d_in is in place; otherwise the ranges must not overlap at all ("overlaps",
+ *   SV_ERR_ARG), and the input is only read.  `form` covers the data and the shift.  All mod r:
+ *   every output is determined bit for bit.  log_n == 0 is legal: a checked copy.
+ *   A transform takes ceil(log_n / 10) launches (csrc/ntt.hip); with two or more the call holds one
+ *   image of the data (count n elements) in pooled scratch.  Root tables: 1 MiB per device, built at
+ *   the device's first call and kept, whatever log_n.
+ * Checked before any device work, in this order: bad form, a direction that is neither value, a null
+ * d_in or d_out, a pointer not 16-byte aligned SV_ERR_ARG; count == 0 SV_ERR_EMPTY; log_n >
+ * SV_NTT_MAX_LOG or count 2^log_n > 2^28 SV_ERR_LEN; a shift not below r SV_ERR_ARG ("not reduced");
+ * a shift equal to zero SV_ERR_ARG; the partial overlap SV_ERR_ARG.  An element not below r is
+ * SV_ERR_ARG ("not reduced") for that call, found on the device in the first pass: d_out is then
+ * unspecified, nothing outside it is written, and the next call is exact.  Points 1 and 2 of
+ * "Streams" apply (ordered after `stream`, synchronous); re-entrant from any number of threads.
+ * SVGPU_NTT_TILE_LOG = 1 .. 10 (read per call) lowers the widest pass for that call: a test switch
+ * that makes the multi-pass paths run at tiny sizes.
+ * Not covered: host buffers (a caller uploads first); G1 transforms (a Lagrange-basis base set);
+ * multi-device transforms; bit-reversed orders on either side.                                 */
+#define SV_NTT_MAX_LOG 26
+enum { SV_NTT_FORWARD = 0, SV_NTT_INVERSE = 1 };
+int sv_bn254_fr_root_of_unity(uint32_t log_n, int form, sv_fe* out) SV_NOEXCEPT;
+int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size_t count,
+                           int direction, const sv_fe* shift, int form, int device,
+                           void* stream) SV_NOEXCEPT;
+
 /* ---- Poseidon sponge over BN254 Fr --------------------------
  * x^5 HADES permutation, width t = 3 (R_F 8, R_P 57, rate 2: the SDK's PoseidonTranscript,
  * snark-verifier-sdk/src/halo2.rs:52-71) or t = 5 (R_F 8, R_P 60, rate 4).  States are t

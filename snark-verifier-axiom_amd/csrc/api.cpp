@@ -23,6 +23,7 @@
 #include "kzg_open.hpp"
 #include "msm.hpp"
 #include "msm_batch.hpp"
+#include "ntt.hpp"
 #include "poseidon.hpp"
 #include "runtime.hpp"
 
@@ -1896,6 +1897,105 @@ int sv_bn254_shplonk_witness_device(uint64_t handle, size_t offset, const sv_shp
     return SV_ERR_ARG;
   }
   jacobian_out(w, out_w_prime_partial);
+  return SV_OK;
+  SV_GUARD_END
+}
+
+// ---- Fr NTT on the device: forward, inverse and coset transforms (csrc/ntt.hip) ----
+namespace {
+// SVGPU_NTT_TILE_LOG = 1 .. kNttTileLog, read per call; anything else is the default
+uint32_t ntt_tile_log() {
+  const char* e = getenv("SVGPU_NTT_TILE_LOG");
+  if (!e || !*e) return kNttTileLog;
+  char* end = nullptr;
+  const long v = strtol(e, &end, 10);
+  if (*end != '\0' || v < 1 || v > (long)kNttTileLog) return kNttTileLog;
+  return (uint32_t)v;
+}
+}  // namespace
+
+int sv_bn254_fr_root_of_unity(uint32_t log_n, int form, sv_fe* out) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!out) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  return fr_root_of_unity(log_n, form, out);
+  SV_GUARD_END
+}
+
+int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size_t count, int direction,
+                           const sv_fe* shift, int form, int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (direction != SV_NTT_FORWARD && direction != SV_NTT_INVERSE) {
+    sv::set_error("direction %d is neither SV_NTT_FORWARD nor SV_NTT_INVERSE", direction);
+    return SV_ERR_ARG;
+  }
+  if (!d_in || !d_out) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15u) {
+    sv::set_error("d_in and d_out must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (count == 0) {
+    sv::set_error("the batch should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (log_n > SV_NTT_MAX_LOG || count > ((size_t(1) << 28) >> log_n)) {
+    sv::set_error("log_n = %u, count = %zu: beyond 2^%d points per transform or 2^28 elements per call", log_n, count,
+                  SV_NTT_MAX_LOG);
+    return SV_ERR_LEN;
+  }
+  NttCall call{};
+  call.has_shift = false;
+  if (shift) {
+    const F g = fe_in(*shift);
+    if (!host::f_is_reduced(g, host::R64)) {
+      sv::set_error("shift not reduced mod the scalar field order");
+      return SV_ERR_ARG;
+    }
+    if ((shift->l[0] | shift->l[1] | shift->l[2] | shift->l[3]) == 0) {
+      sv::set_error("shift is zero: the coset has no inverse");
+      return SV_ERR_ARG;
+    }
+    sv_fe one = {{1, 0, 0, 0}};
+    if (form == SV_MONTGOMERY) one = poly_fr_one();
+    call.has_shift = memcmp(shift->l, one.l, sizeof one.l) != 0;
+    call.shift = *shift;
+  }
+  const size_t bytes = (count << log_n) * sizeof(sv_fe);
+  const uintptr_t ib = (uintptr_t)d_in, ob = (uintptr_t)d_out;
+  if (ib != ob && ib < ob + bytes && ob < ib + bytes) {
+    sv::set_error("d_out overlaps d_in without being d_in (in place is d_out == d_in)");
+    return SV_ERR_ARG;
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  call.d_in = d_in;
+  call.d_out = d_out;
+  call.log_n = log_n;
+  call.count = count;
+  call.inverse = direction == SV_NTT_INVERSE;
+  call.form = form;
+  call.tile_log = ntt_tile_log();
+  SV_TRY(ws->reserve(ntt_scratch_bytes(log_n, count, call.tile_log)));
+  SV_TRY(ws->reserve_pinned(kNttHeadBytes));
+  SV_TRY(ntt_enqueue(call, device, ws->buf, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned, ws->buf + kNttErrOffset, sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl.armed = false;
+  uint32_t errv;
+  memcpy(&errv, ws->pinned, sizeof errv);
+  if (errv) {
+    sv::set_error("invalid input: element not reduced mod r");
+    return SV_ERR_ARG;
+  }
   return SV_OK;
   SV_GUARD_END
 }

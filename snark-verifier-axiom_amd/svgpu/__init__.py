@@ -48,5 +48,23 @@ def poly_div_roots_device(coeffs, roots, **kwargs):
     return run(coeffs, roots, **kwargs)
 
 
+def root_of_unity(k: int, form: int = SV_CANONICAL) -> int:
+    """omega_k, the reference's root_of_unity(k) (util/arithmetic.rs:89-96; k <= 28), as a canonical
+    int.  `form` is the form the library is asked for: the value returned is the same."""
+    import ctypes
+
+    from . import encoding as enc
+    from ._lib import check, sv_fe
+    out = sv_fe()
+    check(lib.sv_bn254_fr_root_of_unity(k, form, ctypes.byref(out)), "sv_bn254_fr_root_of_unity")
+    return enc.fr_from_struct(out, form)
+
+
+def ntt_device(data, **kwargs):
+    """svgpu.device.ntt_device (imported on first use: that module needs torch)."""
+    from .device import ntt_device as run
+    return run(data, **kwargs)
+
+
 def version() -> str:
     return lib.sv_version().decode()

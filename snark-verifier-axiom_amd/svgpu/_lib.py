@@ -21,6 +21,10 @@ SV_OK, SV_ERR_EMPTY, SV_ERR_LEN, SV_ERR_ARG, SV_ERR_DEVICE, SV_ERR_OOM = range(6
 SV_OPEN_BATCH_MAX = 4096  # polynomials per batched opening
 SV_EVAL_POINTS_MAX = 16   # points per evaluation call, roots per division, points per SHPLONK set
 
+SV_NTT_MAX_LOG = 26        # log2 of the longest transform
+SV_NTT_FORWARD = 0
+SV_NTT_INVERSE = 1
+
 SV_ENC_HALO2_COMPRESSED = 0
 SV_ENC_EVM = 1
 
@@ -147,6 +151,9 @@ PROTOTYPES = [
     ("sv_bn254_shplonk_witness_device", c_int, [c_uint64, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                                  POINTER(sv_fe), POINTER(sv_fe), c_int, c_void_p, c_void_p, c_uint64,
                                                  POINTER(sv_g1_jacobian)]),
+    ("sv_bn254_fr_root_of_unity", c_int, [c_uint32, c_int, POINTER(sv_fe)]),
+    ("sv_bn254_fr_ntt_device", c_int, [c_void_p, c_void_p, c_uint32, c_size_t, c_int, c_void_p, c_int, c_int,
+                                        c_void_p]),
     ("sv_bn254_poseidon_permute", c_int, [c_void_p, c_size_t, c_int, c_int]),
     ("sv_bn254_poseidon_permute_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_squeeze", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

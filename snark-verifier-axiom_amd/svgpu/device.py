@@ -197,6 +197,34 @@ def poly_div_roots_device(coeffs: torch.Tensor, roots, form: int = _lib.SV_MONTG
     return out[:max(n - K, 0)]
 
 
+def ntt_device(data: torch.Tensor, inverse: bool = False, shift: Optional[int] = None,
+               form: int = _lib.SV_MONTGOMERY, out: torch.Tensor = None) -> torch.Tensor:
+    """NTT of HBM-resident Fr data: an (n, 4) int64 tensor of limbs in `form` is one transform, a
+    (count, n, 4) tensor `count` transforms back to back; n is a power of two (else LengthError).
+    Forward: out[j] = sum_i data[i] (shift omega^j)^i with omega = root_of_unity(log2 n); inverse=True
+    is its exact inverse; natural order on both sides.  shift: a canonical int, None = 1.
+    out=None allocates, out=data is in place; any other `out` (same shape) must not overlap data."""
+    d = _dev_index(data)
+    if data.dtype != torch.int64 or data.dim() not in (2, 3) or data.shape[-1] != 4 or not data.is_contiguous():
+        raise _lib.ArgumentError("ntt: data is a contiguous (n, 4) or (count, n, 4) int64 tensor of limbs")
+    n = data.shape[-2]
+    count = data.shape[0] if data.dim() == 3 else 1
+    if n == 0 or n & (n - 1):
+        raise _lib.LengthError(f"ntt: {n} rows per transform is not a power of two")
+    if out is None:
+        out = torch.empty_like(data)
+    elif (out.device != data.device or out.dtype != torch.int64 or not out.is_contiguous()
+          or out.shape != data.shape):
+        raise _lib.LengthError(f"ntt: out must be a contiguous {tuple(data.shape)} int64 tensor on {data.device}")
+    gs = enc.fr_struct(shift, form) if shift is not None else None
+    _lib.check(_lib.lib.sv_bn254_fr_ntt_device(data.data_ptr(), out.data_ptr(), n.bit_length() - 1, count,
+                                               _lib.SV_NTT_INVERSE if inverse else _lib.SV_NTT_FORWARD,
+                                               ctypes.byref(gs) if gs is not None else None, form, d,
+                                               _stream_handle(data.device)),
+               "sv_bn254_fr_ntt_device")
+    return out
+
+
 def last_msm_stats() -> dict:
     s = _lib.sv_msm_stats()
     _lib.check(_lib.lib.sv_msm_last_stats(ctypes.byref(s)), "sv_msm_last_stats")

@@ -88,6 +88,10 @@ pub struct SvShplonkSet {
 }
 /// sv_shplonk_set's limit on the points of one set (and of one evaluation call).
 pub const SV_EVAL_POINTS_MAX: usize = 16;
+/// log2 of the longest transform sv_bn254_fr_ntt_device takes, and its two directions.
+pub const SV_NTT_MAX_LOG: u32 = 26;
+pub const SV_NTT_FORWARD: c_int = 0;
+pub const SV_NTT_INVERSE: c_int = 1;
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct SvMsmStats {
@@ -184,6 +188,13 @@ extern "C" {
     pub fn sv_bn254_fr_poly_div_roots_device(d_coeffs: *const SvFe, n: usize, roots: *const SvFe, k: usize,
                                              form: c_int, device: c_int, stream: *mut c_void,
                                              d_quotient: *mut SvFe) -> c_int;
+    /// omega_k = the reference's root_of_unity(k) (util/arithmetic.rs:89-96), host only.
+    pub fn sv_bn254_fr_root_of_unity(log_n: u32, form: c_int, out: *mut SvFe) -> c_int;
+    /// NTT of `count` transforms of 2^log_n elements in HBM: direction SV_NTT_FORWARD / SV_NTT_INVERSE,
+    /// `shift` a host pointer (null = 1), d_out == d_in in place.
+    pub fn sv_bn254_fr_ntt_device(d_in: *const SvFe, d_out: *mut SvFe, log_n: u32, count: usize,
+                                  direction: c_int, shift: *const SvFe, form: c_int, device: c_int,
+                                  stream: *mut c_void) -> c_int;
     pub fn sv_bn254_shplonk_work_elems(n_sets: usize, n: usize, elems: *mut u64) -> c_int;
     pub fn sv_bn254_shplonk_quotient_device(handle: u64, offset: usize, d_polys: *const *const SvFe,
                                             lens: *const u64, m: usize, sets: *const SvShplonkSet, n_sets: usize,
