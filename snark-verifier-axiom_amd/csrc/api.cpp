@@ -23,6 +23,7 @@
 #include "kzg_open.hpp"
 #include "msm.hpp"
 #include "msm_batch.hpp"
+#include "msm_batch_plan.hpp"
 #include "ntt.hpp"
 #include "poseidon.hpp"
 #include "runtime.hpp"
@@ -616,30 +617,13 @@ int sv_bn254_g1_msm_batch(const sv_g1_affine* bases, const sv_fe* scalars, const
   if (count > 0x7fffffffull) return SV_ERR_LEN;
   if (resolve_gpus(1) == 0) return SV_ERR_DEVICE;
   const int dev = runtime_device_id(0);
-  size_t big_limit = 4096;
-  if (const char* e = getenv("SVGPU_BATCH_MAX")) big_limit = strtoull(e, nullptr, 10);
   const uint64_t base = offsets[0], total = offsets[count] - base;
   std::vector<uint64_t> off(offsets, offsets + count + 1);
   for (auto& o : off) o -= base;
-  // The fused batch kernel costs about one Horner chain (~0.65 ms) whatever the batch size, so in a
-  // tiny batch (at most SVGPU_BATCH_SEQ_MAX MSMs) the MSMs above kSmallMsmTerms terms go through the
-  // single-MSM pipeline one by one.  MSMs of at most kSmallMsmTerms terms stay in the batch: a batch
-  // of only such MSMs passes no id map, so msm_batch_device can take its small-batch route (window
-  // sums on the device, one host Horner per MSM: 0.17-0.20 ms for 1-16 MSMs of 64 terms).
-  size_t seq_max = 4;
-  if (const char* e = getenv("SVGPU_BATCH_SEQ_MAX")) seq_max = strtoull(e, nullptr, 10);
-  if (count <= seq_max) big_limit = std::min(big_limit, kSmallMsmTerms);
+  // the long MSMs go through the single-MSM pipeline one by one, the others stay in the batch
   std::vector<uint32_t> small_ids, big_ids;
   size_t max_small = 0;
-  for (size_t k = 0; k < count; k++) {
-    const size_t m = off[k + 1] - off[k];
-    if (m > big_limit) {
-      big_ids.push_back((uint32_t)k);
-    } else {
-      small_ids.push_back((uint32_t)k);
-      max_small = std::max(max_small, m);
-    }
-  }
+  batch_split(off.data(), count, batch_tuning(), &small_ids, &big_ids, &max_small);
   Staging sg(dev);
   SV_TRY(sg.init({total * sizeof(sv_g1_affine), total * sizeof(sv_fe), (count + 1) * sizeof(uint64_t),
                   count * sizeof(uint32_t), count * sizeof(sv_g1_affine)}));

@@ -8,6 +8,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 namespace sv {
 namespace host {
@@ -185,6 +186,30 @@ inline void x_to_affine(const Xyzz& p, F& x, F& y) {
   F izz = f_sqr(iz);
   x = f_mul(p.X, izz);
   y = f_mul(p.Y, izzz);
+}
+
+// n points -> affine limbs out[8 k .. 8 k + 8) = (x, y), Montgomery or canonical, with ONE inversion
+// (Montgomery's trick over the ZZZ of the non-identity points): x = X / ZZ = X (ZZ ZZZ^-1)^2,
+// y = Y / ZZZ; the identity is (0, 0)
+inline void x_to_affine_batch(const Xyzz* p, size_t n, bool montgomery, uint64_t* out) {
+  std::vector<F> pre(n);
+  F run = f_one();
+  for (size_t k = 0; k < n; k++) {
+    pre[k] = run;  // product of the earlier non-identity ZZZ
+    if (!x_is_identity(p[k])) run = f_mul(run, p[k].ZZZ);
+  }
+  F inv = f_inv(run);
+  memset(out, 0, 64 * n);
+  for (size_t k = n; k-- > 0;) {
+    if (x_is_identity(p[k])) continue;
+    const F izzz = f_mul(inv, pre[k]);
+    inv = f_mul(inv, p[k].ZZZ);
+    const F iz = f_mul(izzz, p[k].ZZ);
+    F x = f_mul(p[k].X, f_sqr(iz)), y = f_mul(p[k].Y, izzz);
+    if (!montgomery) x = f_from_mont(x), y = f_from_mont(y);
+    memcpy(out + 8 * k, x.l, 32);
+    memcpy(out + 8 * k + 4, y.l, 32);
+  }
 }
 
 // Jacobian (x = X/Z^2, y = Y/Z^3) <-> XYZZ.   XYZZ(X, Y, ZZ, ZZZ) == Jacobian(X*ZZ*ZZZ^2 ... ) is

@@ -19,9 +19,6 @@
 // size.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -29,6 +26,7 @@
 #include "glv.hpp"
 #include "host_ec.hpp"
 #include "msm_batch.hpp"
+#include "msm_batch_plan.hpp"
 #include "quad.hpp"
 #include "runtime.hpp"
 
@@ -36,7 +34,7 @@ namespace sv {
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kBatchThreads;
 
 __device__ __forceinline__ Fq ld_fq(const uint32_t* p) {
   const uint4* q = reinterpret_cast<const uint4*>(p);
@@ -75,20 +73,8 @@ __device__ __forceinline__ G1Xyzz smul_small(const G1Xyzz& p, uint32_t k) {
   return r;
 }
 
-// GLV (glv.hpp): every term k P is split into k1 P + k2 phi(P) with |k_i| < 2^127, so the windows
-// cover 128 bits and the per-MSM Horner chain is ~128 doublings instead of ~255.
-template <int C>
-struct BatchCfg {
-  static constexpr int W = (128 + C - 1) / C;  // signed digits of a < 2^127 half scalar
-  static constexpr int B = 1 << (C - 1);
-  static constexpr int G = B < 64 ? B : 64;  // lanes per window
-  static constexpr int BPL = B / G;          // buckets per lane
-  static constexpr int WPB = kThreads / G;   // windows per block
-  static constexpr int WG = (W + WPB - 1) / WPB;  // window groups (blockIdx.y)
-  static constexpr int NCH = C <= 6 ? 128 : 256;
-};
-
 // Step 1 + 2: block (msm, window group) -> window sums Tg[id * W + w] (XYZZ, Montgomery).
+// BatchCfg<C>: msm_batch_plan.hpp
 template <int C>
 __global__ void __launch_bounds__(kThreads) k_msm_batch_windows(const G1Aff* __restrict__ bases,
                                                                  const Fr* __restrict__ scalars,
@@ -124,7 +110,7 @@ __global__ void __launch_bounds__(kThreads) k_msm_batch_windows(const G1Aff* __r
 #pragma unroll
         for (int i = 0; i < 8; i++) s.v[i] = t.v[i];
       }
-      if (!s.is_reduced()) atomicOr(err, 2u);
+      if (!s.is_reduced()) atomicOr(err, kErrScalar);
       if (mont) s = fe_from_mont(s);
       uint32_t hv[2][4];
       glv_split(s.v, hv[0], hv[1]);
@@ -195,7 +181,7 @@ __global__ void __launch_bounds__(kThreads) k_msm_batch_windows(const G1Aff* __r
             if (bidx) {  // base table: term -> table row (fixed bases resident on the device)
               const uint32_t ti = bidx[bi];
               if (ti >= tlen) {
-                atomicOr(err, 4u);
+                atomicOr(err, kErrIndex);
                 continue;
               }
               bi = ti;
@@ -203,7 +189,7 @@ __global__ void __launch_bounds__(kThreads) k_msm_batch_windows(const G1Aff* __r
             const uint32_t* bp = reinterpret_cast<const uint32_t*>(bases + bi);
             Fq x = ld_fq(bp), y = ld_fq(bp + 8);
             if (!x.is_reduced() || !y.is_reduced()) {  // same contract as the single-MSM path
-              atomicOr(err, 1u);
+              atomicOr(err, kErrBase);
               continue;
             }
             if (x.is_zero() && y.is_zero()) continue;  // identity base
@@ -237,11 +223,8 @@ __global__ void __launch_bounds__(kThreads) k_msm_batch_windows(const G1Aff* __r
 // (quad.hpp), then sum_b (b + 1) S_b = sum_b R_b over the suffix sums R_b = sum_{b' >= b} S_b': a
 // 4-level scan and a 4-level tree across the wave's 16 quads.  The old kernel ran ~20 dependent
 // whole additions per window on one wave per SIMD (a per-lane bucket chain, a divergent weighting
-// double-and-add, a shuffle tree); here every level is one quad operation.
-constexpr int kQC = 5;                       // window bits of the quad path
-constexpr int kQB = 1 << (kQC - 1);          // 16 buckets: one quad each in a 64-lane wave
-constexpr int kQW = BatchCfg<kQC>::W;        // 26 windows of a 128-bit GLV half
-constexpr int kQMaxTerms = 256;              // half-terms of one window sorted in LDS at once
+// double-and-add, a shuffle tree); here every level is one quad operation.  (kQC, kQB, kQW,
+// kQMaxTerms: msm_batch_plan.hpp)
 
 __global__ void __launch_bounds__(kThreads) k_batch_prep(const G1Aff* __restrict__ bases,
                                                          const Fr* __restrict__ scalars,
@@ -263,13 +246,13 @@ __global__ void __launch_bounds__(kThreads) k_batch_prep(const G1Aff* __restrict
 #pragma unroll
     for (int j = 0; j < 8; j++) s.v[j] = q.v[j];
   }
-  if (!s.is_reduced()) atomicOr(err, 2u);
+  if (!s.is_reduced()) atomicOr(err, kErrScalar);
   if (mont) s = fe_from_mont(s);
   uint64_t bi = t;
   if (bidx) {
     const uint32_t ti = bidx[t];
     if (ti >= tlen) {
-      atomicOr(err, 4u);
+      atomicOr(err, kErrIndex);
       s = Fr::zero();
       bi = 0;
     } else {
@@ -306,7 +289,7 @@ __global__ void __launch_bounds__(kThreads) k_batch_prep(const G1Aff* __restrict
   const uint32_t* bp = reinterpret_cast<const uint32_t*>(bases + bi);
   Fq x = ld_fq(bp), y = ld_fq(bp + 8);
   if (!x.is_reduced() || !y.is_reduced()) {  // same contract as the single-MSM path
-    atomicOr(err, 1u);
+    atomicOr(err, kErrBase);
     x = y = Fq::zero();
   }
   const bool ident = x.is_zero() && y.is_zero();
@@ -507,7 +490,6 @@ __device__ __forceinline__ void bucket_window(BucketSmem& sm, uint32_t k, uint32
 // row), U_4 = S_15 -- on wave 0.  Every quad addition runs through ONE call site (a loop over the
 // steps), so the code a wave fetches stays small.  The host places U_k at exponent 5 w + k of one
 // Horner.
-constexpr int kUPerWin = kQC;  // U_0 .. U_4
 constexpr int kUwThreads = 256, kUL = kUwThreads / kQB;  // 16 lanes per bucket
 __global__ void __launch_bounds__(kUwThreads) k_batch_uwin(const uint64_t* __restrict__ off, uint32_t max_terms,
                                                            const uint8_t* __restrict__ dig, const G1Aff* __restrict__ pts,
@@ -598,7 +580,7 @@ __device__ __forceinline__ void wait_ready(const uint32_t* f, uint32_t* err, uin
   while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
     __builtin_amdgcn_s_sleep(8);
     if (++spins > spin_max) {
-      if (threadIdx.x == 0) atomicOr(err, 8u);
+      if (threadIdx.x == 0) atomicOr(err, kErrWait);
       break;
     }
   }
@@ -669,8 +651,6 @@ __global__ void __launch_bounds__(64) k_batch_horner_b(const G1Xyzz* __restrict_
 // wave waits for each window with an acquire load.  The host only takes this path while the
 // Horner waves are a small fraction of the resident-wave capacity (count <= kFuseMax), so bucket
 // blocks always find slots and every wait ends.
-constexpr uint32_t kFuseMax = 512;
-
 __global__ void __launch_bounds__(64) k_batch_fused(const uint64_t* __restrict__ off, const uint32_t* __restrict__ ids,
                                                     uint32_t count, uint32_t max_terms,
                                                     const uint8_t* __restrict__ dig, const G1Aff* __restrict__ pts,
@@ -931,11 +911,11 @@ __global__ void __launch_bounds__(kThreads) k_msm_batch_fixed(const G1Aff* __res
 #pragma unroll
         for (int i = 0; i < 8; i++) s.v[i] = t.v[i];
       }
-      if (!s.is_reduced()) atomicOr(err, 2u);
+      if (!s.is_reduced()) atomicOr(err, kErrScalar);
       if (mont) s = fe_from_mont(s);
       row = bidx[c0 + tid];
       if (row >= rows) {
-        atomicOr(err, 4u);
+        atomicOr(err, kErrIndex);
         s = Fr::zero();
       }
       uint32_t carry = 0, sg = 0;
@@ -1018,50 +998,109 @@ __global__ void __launch_bounds__(kThreads) k_msm_batch_fixed(const G1Aff* __res
   }
 }
 
-}  // namespace
+// ---- Host half.  Which route a call takes, what it reserves and where every buffer lies is
+// decided in msm_batch_plan.hpp (batch_plan, batch_buffers); here a driver takes its workspace from
+// the layout and launches the route's kernels.
 
-static std::atomic<uint64_t> g_fused_redone{0};  // fused launches redone by the two-kernel path
-
-int msm_batch_window_bits(size_t max_terms) {
-  if (const char* e = getenv("SVGPU_BATCH_WINDOW_BITS")) {
-    const int c = atoi(e);
-    if (c == 5 || c == 8) return c;
-  }
-  return max_terms <= 256 ? 5 : 8;
+template <class T>
+T* buf_at(char* base, size_t off) {
+  return off == MsmLayout::kAbsent ? nullptr : reinterpret_cast<T*>(base + off);
 }
 
-// Small plain batches (round 5): the window sums on the device and one host Horner per MSM on the
-// host pool (msm_batch_windows_host) instead of the fused kernel, whose one-wave Horner chain takes
-// ~0.65 ms whatever the batch size (one 64-term MSM as long as 128 of them,
-// profiles/r05_batch_floor_probe.log).  The host costs ~35 us per MSM, spread over the pool:
-// 0.17-0.20 ms for 1-16 MSMs of 64 terms, 0.47 at 64, even at ~100, slower at 128
-// (profiles/r05_batch_host_route_ab.log).  SVGPU_BATCH_HOST_MAX sets the largest such batch (0: never).
-constexpr size_t kBatchHostMax = 64;
-static int msm_batch_small_host(const void* d_bases, const void* d_scalars, const uint64_t* d_offsets, size_t count,
-                                size_t max_terms, int form, int device, hipStream_t stream, void* d_out) {
+// One call as its kernels see it
+struct BatchCall {
+  const G1Aff* bases;
+  const Fr* scalars;
+  const uint64_t* off;
+  const uint32_t* ids;
+  const uint32_t* bidx;
+  uint64_t table_len;
+  int mont, mont_b;  // scalars and outputs / bases in Montgomery form
+  G1Aff* out;
+  uint32_t* err;     // the error word; a fused launch's window flags follow it
+  G1Xyzz* T;
+  uint8_t* dig;
+  G1Aff* pts;
+  hipStream_t st;
+};
+
+void launch_prep(const BatchCall& a, size_t count, size_t max_terms) {
+  hipLaunchKernelGGL(k_batch_prep, dim3((uint32_t)count, (uint32_t)((max_terms + kThreads - 1) / kThreads)),
+                     dim3(kThreads), 0, a.st, a.bases, a.scalars, a.off, a.ids, a.mont, (uint32_t)max_terms, a.dig,
+                     a.pts, a.err, a.bidx, a.table_len, a.mont_b);
+}
+
+// The window Horner in quad form (k_msm_batch_horner_q<c>): 16 MSMs per wave
+void launch_horner_q(decltype(&k_msm_batch_horner_q<kQC>) kernel, const BatchCall& a, size_t count) {
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)((count + 15) / 16)), dim3(64), 0, a.st, a.T, a.ids, (uint32_t)count,
+                     a.mont, a.out);
+}
+
+void launch_quad_windows(const BatchCall& a, const BatchPlan& p) {
+  hipLaunchKernelGGL(k_batch_windows_q, dim3((uint32_t)p.count, (uint32_t)kQW), dim3(64), 0, a.st, a.off, a.ids,
+                     (uint32_t)p.max_terms, a.dig, a.pts, a.T);
+  launch_horner_q(k_msm_batch_horner_q<kQC>, a, p.count);
+}
+
+// The per-lane window sums, then the window Horner: in quad form, or one wave per MSM
+template <int C>
+void launch_lane_windows(const BatchCall& a, const BatchPlan& p) {
+  hipLaunchKernelGGL(k_msm_batch_windows<C>, dim3((uint32_t)p.count, p.WG), dim3(kThreads), 0, a.st, a.bases,
+                     a.scalars, a.off, a.ids, a.mont, a.T, a.err, a.bidx, a.table_len, a.mont_b);
+  if (p.quad_horner)
+    launch_horner_q(k_msm_batch_horner_q<C>, a, p.count);
+  else
+    hipLaunchKernelGGL(k_msm_batch_horner<C>, dim3((uint32_t)p.count), dim3(64), 0, a.st, a.T, a.ids, a.mont, a.out);
+}
+
+// the BucketHorner route, and the redo of a fused launch that timed out
+void launch_bucket_horner(const BatchCall& a, const BatchPlan& p) {
+  hipLaunchKernelGGL(k_batch_buckets_q, dim3((uint32_t)p.count, (uint32_t)kQW), dim3(64), 0, a.st, a.off, a.ids,
+                     (uint32_t)p.max_terms, a.dig, a.pts, a.T);
+  hipLaunchKernelGGL(k_batch_horner_b, dim3((uint32_t)p.count), dim3(64), 0, a.st, a.T, a.ids, a.mont, a.out);
+}
+
+void launch_fused(const BatchCall& a, const BatchPlan& p) {
+  hipLaunchKernelGGL(k_batch_fused, dim3((uint32_t)(p.count * (1 + p.bw))), dim3(64), 0, a.st, a.off, a.ids,
+                     (uint32_t)p.count, (uint32_t)p.max_terms, a.dig, a.pts, a.T, a.err + 1, a.err, a.mont, a.out, p.bw,
+                     p.spin_max);
+}
+
+// Launch errors, then the layout's copy-back block (the error word first) into pinned memory;
+// returns once it has landed
+int copy_back(Workspace* ws, const BatchBuffers& b, uint32_t* ev) {
+  SV_HIP(hipGetLastError());
+  SV_HIP(hipMemcpyAsync(ws->pinned + b.pin_back, ws->buf + b.flags, b.back_bytes, hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  memcpy(ev, ws->pinned + b.pin_back, 4);
+  return SV_OK;
+}
+
+// The argument error an error word stands for.  kErrWait is none: msm_batch_device redoes the launch.
+int batch_error(uint32_t ev, unsigned long long table_len) {
+  if (ev & kErrBase) {
+    set_error("msm_batch: base coordinate not reduced mod p");
+    return SV_ERR_ARG;
+  }
+  if (ev & kErrScalar) {
+    set_error("msm_batch: scalar not reduced (>= r)");
+    return SV_ERR_ARG;
+  }
+  if (ev & kErrIndex) {
+    set_error("msm_batch: base index out of the table (>= %llu)", table_len);
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+
+// The HostHorner route: msm_batch_windows_host, then the affine outputs in `form` with one inversion
+int msm_batch_small_host(const void* d_bases, const void* d_scalars, const uint64_t* d_offsets, size_t count,
+                         size_t max_terms, int form, int device, hipStream_t stream, void* d_out) {
   std::vector<host::Xyzz> acc(count);
   SV_TRY(msm_batch_windows_host(d_bases, d_scalars, d_offsets, count, max_terms, form, form, device, stream,
                                 acc.data()));
-  // affine in `form` with ONE inversion (Montgomery's trick over the ZZZ of the non-identity sums):
-  // x = X / ZZ = X (ZZ ZZZ^-1)^2, y = Y / ZZZ; the identity is (0, 0)
-  std::vector<host::F> pre(count);
-  host::F run = host::f_one();
-  for (size_t k = 0; k < count; k++) {
-    pre[k] = run;  // product of the earlier non-identity ZZZ
-    if (!host::x_is_identity(acc[k])) run = host::f_mul(run, acc[k].ZZZ);
-  }
-  host::F inv = host::f_inv(run);
-  std::vector<uint64_t> h(8 * count, 0);
-  for (size_t k = count; k-- > 0;) {
-    if (host::x_is_identity(acc[k])) continue;
-    const host::F izzz = host::f_mul(inv, pre[k]);
-    inv = host::f_mul(inv, acc[k].ZZZ);
-    const host::F iz = host::f_mul(izzz, acc[k].ZZ);
-    host::F x = host::f_mul(acc[k].X, host::f_sqr(iz)), y = host::f_mul(acc[k].Y, izzz);
-    if (form != SV_MONTGOMERY) x = host::f_from_mont(x), y = host::f_from_mont(y);
-    memcpy(&h[8 * k], x.l, 32);
-    memcpy(&h[8 * k + 4], y.l, 32);
-  }
+  std::vector<uint64_t> h(8 * count);
+  host::x_to_affine_batch(acc.data(), count, form == SV_MONTGOMERY, h.data());
   // on the caller's stream (no null-stream implicit sync); this route is synchronous for the host
   // anyway (msm_batch_windows_host waited for the window sums), so wait for the copy of `h`
   SV_HIP(hipSetDevice(device));
@@ -1069,6 +1108,10 @@ static int msm_batch_small_host(const void* d_bases, const void* d_scalars, cons
   SV_HIP(hipStreamSynchronize(raw_stream(stream)));
   return SV_OK;
 }
+
+}  // namespace
+
+int msm_batch_window_bits(size_t max_terms) { return batch_window_bits(max_terms, batch_tuning()); }
 
 int msm_batch_device(const void* d_bases, const void* d_scalars, const uint64_t* d_offsets, const uint32_t* d_ids,
                      size_t count, size_t max_terms, int form, int device, hipStream_t stream, void* d_out,
@@ -1078,144 +1121,53 @@ int msm_batch_device(const void* d_bases, const void* d_scalars, const uint64_t*
     set_error("msm_batch: count = %zu too large", count);
     return SV_ERR_LEN;
   }
-  {
-    const char* hm = getenv("SVGPU_BATCH_HOST_MAX");  // read per call
-    const size_t host_max = hm ? (size_t)strtoull(hm, nullptr, 10) : kBatchHostMax;
-    if (!d_ids && !d_bidx && count <= host_max && max_terms >= 1 && max_terms <= (size_t)kQMaxTerms &&
-        msm_batch_window_bits(max_terms) == kQC)
-      return msm_batch_small_host(d_bases, d_scalars, d_offsets, count, max_terms, form, device, stream, d_out);
-  }
+  BatchPlan p = batch_plan(count, max_terms, d_ids != nullptr, d_bidx != nullptr, batch_tuning());
+  if (p.route == BatchRoute::HostHorner)
+    return msm_batch_small_host(d_bases, d_scalars, d_offsets, count, max_terms, form, device, stream, d_out);
   WsLease lease(device, stream);
   if (!lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = lease.get();
-  hipStream_t st = ws->stream;
-  const int c = msm_batch_window_bits(max_terms);
-  const int W = c == 5 ? BatchCfg<5>::W : BatchCfg<8>::W;
-  const int WG = c == 5 ? BatchCfg<5>::WG : BatchCfg<8>::WG;
-  // SVGPU_BATCH_QUAD=0: the round-2 kernels (per-lane window sums, one-wave Horner)
-  const bool quad_path = !getenv("SVGPU_BATCH_QUAD") || atoi(getenv("SVGPU_BATCH_QUAD")) != 0;
-  const bool quad_windows = quad_path && c == kQC && max_terms <= (size_t)kQMaxTerms;
-  // bucket-wise Horner (k_batch_buckets_q + k_batch_horner_b; SVGPU_BATCH_BUCKETS=0 keeps the
-  // per-window weighting of k_batch_windows_q): 16 bucket sums per window instead of one window sum,
-  // 53 KB per MSM, so very large batches keep the per-window path
-  const bool bucket_horner = quad_windows && count <= 4096 &&
-                             (!getenv("SVGPU_BATCH_BUCKETS") || atoi(getenv("SVGPU_BATCH_BUCKETS")) != 0);
-  const size_t dig_bytes = quad_windows ? count * kQW * 2 * max_terms : 0;
-  const size_t pts_bytes = quad_windows ? count * 2 * max_terms * sizeof(G1Aff) : 0;
-  const size_t nT = bucket_horner ? count * kQB * kQW : count * W;
-  // one launch for buckets + Horner while the Horner waves stay few (k_batch_fused; SVGPU_BATCH_FUSE=0
-  // runs the two kernels back to back)
-  // HIP promises no co-residency between workgroups of a launch, and the Horner waves of a fused
-  // launch hold their slots while they wait: one fused launch (count <= kFuseMax waves) leaves most
-  // of the chip's wave slots to its bucket blocks, but several at once on one GPU (concurrent
-  // callers, SVGPU_DEVICE_MAP repeats) could fill it with waiting waves.  So at most ONE fused launch
-  // is in flight per physical device; the others take the two-kernel path.  A launch whose wait
-  // times out anyway (error bit 8) is redone below by the two-kernel path, never reported.
-  bool fused = bucket_horner && count <= kFuseMax &&
-               (!getenv("SVGPU_BATCH_FUSE") || atoi(getenv("SVGPU_BATCH_FUSE")) != 0);
-  struct FuseSlot {
-    std::atomic<int>* slot = nullptr;
-    ~FuseSlot() {
-      if (slot) slot->fetch_sub(1, std::memory_order_acq_rel);
-    }
-  } fuse_slot;
-  if (fused) {
-    static std::atomic<int> inflight[64];
-    std::atomic<int>& f = inflight[device & 63];
-    if (f.fetch_add(1, std::memory_order_acq_rel) == 0) {
-      fuse_slot.slot = &f;
-    } else {
-      f.fetch_sub(1, std::memory_order_acq_rel);
-      fused = false;
-    }
+  FuseSlot slot;  // held until the call returns
+  if (p.route == BatchRoute::Fused && !slot.acquire(device)) p = batch_without_slot(p);
+  const BatchBuffers b = batch_buffers(p);
+  SV_TRY(ws->reserve(b.ws.total));
+  SV_TRY(ws->reserve_pinned(b.pin.total));
+  BatchCall a;
+  a.bases = static_cast<const G1Aff*>(d_bases);
+  a.scalars = static_cast<const Fr*>(d_scalars);
+  a.off = d_offsets;
+  a.ids = d_ids;
+  a.bidx = d_bidx;
+  a.table_len = table_len;
+  a.mont = form == SV_MONTGOMERY;
+  a.mont_b = (d_bidx ? base_form : form) == SV_MONTGOMERY;
+  a.out = static_cast<G1Aff*>(d_out);
+  a.err = buf_at<uint32_t>(ws->buf, b.flags);
+  a.T = buf_at<G1Xyzz>(ws->buf, b.T);
+  a.dig = buf_at<uint8_t>(ws->buf, b.dig);
+  a.pts = buf_at<G1Aff>(ws->buf, b.pts);
+  a.st = ws->stream;
+  SV_HIP(hipMemsetAsync(a.err, 0, 4 * (1 + p.nflag), a.st));
+  if (p.route != BatchRoute::LaneWindows) launch_prep(a, count, max_terms);
+  switch (p.route) {
+    case BatchRoute::Fused: launch_fused(a, p); break;
+    case BatchRoute::BucketHorner: launch_bucket_horner(a, p); break;
+    case BatchRoute::QuadWindows: launch_quad_windows(a, p); break;
+    default: p.c == 5 ? launch_lane_windows<5>(a, p) : launch_lane_windows<8>(a, p);
   }
-  const size_t nflag = fused ? count * kQW : 0;
-  SV_TRY(ws->reserve(Workspace::aligned(4 * (1 + nflag)) + Workspace::aligned(nT * sizeof(G1Xyzz)) +
-                     Workspace::aligned(dig_bytes ? dig_bytes : 1) + Workspace::aligned(pts_bytes ? pts_bytes : 1)));
-  SV_TRY(ws->reserve_pinned(256));
-  uint32_t* err = ws->carve<uint32_t>(1 + nflag);  // the error word, then the window flags
-  G1Xyzz* Tg = ws->carve<G1Xyzz>(nT);
-  uint8_t* dig = ws->carve<uint8_t>(dig_bytes ? dig_bytes : 1);
-  G1Aff* pts = ws->carve<G1Aff>(pts_bytes ? pts_bytes / sizeof(G1Aff) : 1);
-  SV_HIP(hipMemsetAsync(err, 0, 4 * (1 + nflag), st));
-  const int mont = form == SV_MONTGOMERY;
-  const int mont_b = (d_bidx ? base_form : form) == SV_MONTGOMERY;
-  const G1Aff* b = static_cast<const G1Aff*>(d_bases);
-  const Fr* s = static_cast<const Fr*>(d_scalars);
-  G1Aff* o = static_cast<G1Aff*>(d_out);
-  const dim3 grid((uint32_t)count, WG);
-  const bool quad_horner = quad_path;
-  if (quad_windows) {
-    hipLaunchKernelGGL(k_batch_prep, dim3((uint32_t)count, (uint32_t)((max_terms + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, st, b, s, d_offsets, d_ids, mont, (uint32_t)max_terms, dig, pts, err, d_bidx,
-                       table_len, mont_b);
-    if (fused) {
-      // SVGPU_BATCH_WAIT_SPINS: the wait bound (default 2^22 sleeps, ~1 s); tests set it to 0 to
-      // force the timeout and the two-kernel redo
-      const char* spins_env = getenv("SVGPU_BATCH_WAIT_SPINS");
-      const uint32_t spin_max = spins_env ? (uint32_t)strtoul(spins_env, nullptr, 10) : (1u << 22);
-      const uint32_t bw = std::min<uint32_t>(kQW, std::max(1, getenv("SVGPU_BATCH_BW") ? atoi(getenv("SVGPU_BATCH_BW")) : 4));
-      hipLaunchKernelGGL(k_batch_fused, dim3((uint32_t)(count * (1 + bw))), dim3(64), 0, st, d_offsets, d_ids,
-                         (uint32_t)count, (uint32_t)max_terms, dig, pts, Tg, err + 1, err, mont, o, bw, spin_max);
-    } else if (bucket_horner) {
-      hipLaunchKernelGGL(k_batch_buckets_q, dim3((uint32_t)count, (uint32_t)kQW), dim3(64), 0, st, d_offsets, d_ids,
-                         (uint32_t)max_terms, dig, pts, Tg);
-      hipLaunchKernelGGL(k_batch_horner_b, dim3((uint32_t)count), dim3(64), 0, st, Tg, d_ids, mont, o);
-    } else {
-      hipLaunchKernelGGL(k_batch_windows_q, dim3((uint32_t)count, (uint32_t)kQW), dim3(64), 0, st, d_offsets, d_ids,
-                         (uint32_t)max_terms, dig, pts, Tg);
-      hipLaunchKernelGGL(k_msm_batch_horner_q<5>, dim3((uint32_t)((count + 15) / 16)), dim3(64), 0, st, Tg, d_ids,
-                         (uint32_t)count, mont, o);
-    }
-  } else if (c == 5) {
-    hipLaunchKernelGGL(k_msm_batch_windows<5>, grid, dim3(kThreads), 0, st, b, s, d_offsets, d_ids, mont, Tg, err,
-                       d_bidx, table_len, mont_b);
-    if (quad_horner)
-      hipLaunchKernelGGL(k_msm_batch_horner_q<5>, dim3((uint32_t)((count + 15) / 16)), dim3(64), 0, st, Tg, d_ids,
-                         (uint32_t)count, mont, o);
-    else
-      hipLaunchKernelGGL(k_msm_batch_horner<5>, dim3((uint32_t)count), dim3(64), 0, st, Tg, d_ids, mont, o);
-  } else {
-    hipLaunchKernelGGL(k_msm_batch_windows<8>, grid, dim3(kThreads), 0, st, b, s, d_offsets, d_ids, mont, Tg, err,
-                       d_bidx, table_len, mont_b);
-    if (quad_horner)
-      hipLaunchKernelGGL(k_msm_batch_horner_q<8>, dim3((uint32_t)((count + 15) / 16)), dim3(64), 0, st, Tg, d_ids,
-                         (uint32_t)count, mont, o);
-    else
-      hipLaunchKernelGGL(k_msm_batch_horner<8>, dim3((uint32_t)count), dim3(64), 0, st, Tg, d_ids, mont, o);
-  }
-  SV_HIP(hipGetLastError());
-  SV_HIP(hipMemcpyAsync(ws->pinned, err, 4, hipMemcpyDeviceToHost, st));
-  SV_HIP(hipStreamSynchronize(st));
   uint32_t ev;
-  memcpy(&ev, ws->pinned, 4);
-  if (ev & 1u) {
-    set_error("msm_batch: base coordinate not reduced mod p");
-    return SV_ERR_ARG;
-  }
-  if (ev & 2u) {
-    set_error("msm_batch: scalar not reduced (>= r)");
-    return SV_ERR_ARG;
-  }
-  if (ev & 4u) {
-    set_error("msm_batch: base index out of the table (>= %llu)", (unsigned long long)table_len);
-    return SV_ERR_ARG;
-  }
-  if (ev & 8u) {
+  SV_TRY(copy_back(ws, b, &ev));
+  SV_TRY(batch_error(ev, table_len));
+  if (ev & kErrWait) {
     // a fused launch's Horner wave gave up waiting (the GPU was full of other waves): its outputs
     // are garbage, so redo the bucket sums and the Horner as two ordered launches
-    SV_HIP(hipMemsetAsync(err, 0, 4, st));
-    hipLaunchKernelGGL(k_batch_buckets_q, dim3((uint32_t)count, (uint32_t)kQW), dim3(64), 0, st, d_offsets, d_ids,
-                       (uint32_t)max_terms, dig, pts, Tg);
-    hipLaunchKernelGGL(k_batch_horner_b, dim3((uint32_t)count), dim3(64), 0, st, Tg, d_ids, mont, o);
+    SV_HIP(hipMemsetAsync(a.err, 0, 4, a.st));
+    launch_bucket_horner(a, p);
     SV_HIP(hipGetLastError());
-    SV_HIP(hipStreamSynchronize(st));
-    g_fused_redone.fetch_add(1, std::memory_order_relaxed);
+    SV_HIP(hipStreamSynchronize(a.st));
   }
   return SV_OK;
 }
-
-uint64_t msm_batch_fused_redone() { return g_fused_redone.load(std::memory_order_relaxed); }
 
 // ---- Small batches with the window Horner on the host (round 5).  A batch of a few MSMs of at most
 // kQMaxTerms terms -- KzgAs::create_proof's two r^i MSMs (accumulation.rs:177-192), a native
@@ -1228,59 +1180,47 @@ int msm_batch_windows_host(const void* d_bases, const void* d_scalars, const uin
                            size_t max_terms, int scalar_form, int base_form, int device, hipStream_t stream,
                            host::Xyzz* out) {
   if (count == 0) return SV_OK;
-  if (max_terms == 0 || max_terms > (size_t)kQMaxTerms || count > 0xffffu) {
+  if (!batch_windows_host_ok(count, max_terms)) {
     set_error("msm_batch_windows_host: %zu MSMs of up to %zu terms (at most %d terms)", count, max_terms, kQMaxTerms);
     return SV_ERR_ARG;
   }
+  const bool single = !d_offsets;  // msm_run_impl's small path: offsets {0, max_terms}
+  if (single && count != 1) return SV_ERR_ARG;
   WsLease lease(device, stream);
   if (!lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = lease.get();
-  hipStream_t st = ws->stream;
-  const size_t nT = count * kQW * kUPerWin;
-  const size_t dig_bytes = count * kQW * 2 * max_terms;
-  const size_t pts_bytes = count * 2 * max_terms * sizeof(G1Aff);
-  const size_t t_off = 256;  // the error word, then the window sums: ONE copy back
-  const size_t back = t_off + nT * sizeof(G1Xyzz);  // bytes copied back
-  SV_TRY(ws->reserve(t_off + Workspace::aligned(nT * sizeof(G1Xyzz)) + Workspace::aligned(dig_bytes) +
-                     Workspace::aligned(pts_bytes) + 256));
-  SV_TRY(ws->reserve_pinned(Workspace::aligned(back) + 16));
-  unsigned char* blk = ws->carve<unsigned char>(t_off + Workspace::aligned(nT * sizeof(G1Xyzz)));
-  uint32_t* err = reinterpret_cast<uint32_t*>(blk);
-  G1Xyzz* Tg = reinterpret_cast<G1Xyzz*>(blk + t_off);
-  uint8_t* dig = ws->carve<uint8_t>(dig_bytes);
-  G1Aff* pts = ws->carve<G1Aff>(pts_bytes / sizeof(G1Aff));
-  if (!d_offsets) {  // one MSM of max_terms terms (msm_run_impl's small path): offsets {0, max_terms}
-    if (count != 1) return SV_ERR_ARG;
-    uint64_t* hoff = reinterpret_cast<uint64_t*>(ws->pinned + Workspace::aligned(back));
+  const BatchBuffers b = batch_windows_host_buffers(count, max_terms, single);
+  SV_TRY(ws->reserve(b.ws.total));
+  SV_TRY(ws->reserve_pinned(b.pin.total));
+  BatchCall a = {};
+  a.bases = static_cast<const G1Aff*>(d_bases);
+  a.scalars = static_cast<const Fr*>(d_scalars);
+  a.off = d_offsets;
+  a.mont = scalar_form == SV_MONTGOMERY;
+  a.mont_b = base_form == SV_MONTGOMERY;
+  a.err = buf_at<uint32_t>(ws->buf, b.flags);
+  a.T = buf_at<G1Xyzz>(ws->buf, b.T);
+  a.dig = buf_at<uint8_t>(ws->buf, b.dig);
+  a.pts = buf_at<G1Aff>(ws->buf, b.pts);
+  a.st = ws->stream;
+  if (single) {
+    uint64_t* hoff = reinterpret_cast<uint64_t*>(ws->pinned + b.pin_off);
     hoff[0] = 0;
     hoff[1] = max_terms;
-    uint64_t* doff = ws->carve<uint64_t>(2);
-    SV_HIP(hipMemcpyAsync(doff, hoff, 16, hipMemcpyHostToDevice, st));
-    d_offsets = doff;
+    uint64_t* doff = buf_at<uint64_t>(ws->buf, b.off);
+    SV_HIP(hipMemcpyAsync(doff, hoff, 16, hipMemcpyHostToDevice, a.st));
+    a.off = doff;
   }
-  SV_HIP(hipMemsetAsync(err, 0, 4, st));
-  hipLaunchKernelGGL(k_batch_prep, dim3((uint32_t)count, (uint32_t)((max_terms + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, st, static_cast<const G1Aff*>(d_bases), static_cast<const Fr*>(d_scalars),
-                     d_offsets, nullptr, scalar_form == SV_MONTGOMERY ? 1 : 0, (uint32_t)max_terms, dig, pts, err,
-                     nullptr, (uint64_t)0, base_form == SV_MONTGOMERY ? 1 : 0);
-  hipLaunchKernelGGL(k_batch_uwin, dim3((uint32_t)count, (uint32_t)kQW), dim3(kUwThreads), 0, st, d_offsets,
-                     (uint32_t)max_terms, dig, pts, Tg);
-  SV_HIP(hipGetLastError());
-  SV_HIP(hipMemcpyAsync(ws->pinned, blk, back, hipMemcpyDeviceToHost, st));
-  SV_HIP(hipStreamSynchronize(st));
+  SV_HIP(hipMemsetAsync(a.err, 0, 4, a.st));
+  launch_prep(a, count, max_terms);
+  hipLaunchKernelGGL(k_batch_uwin, dim3((uint32_t)count, (uint32_t)kQW), dim3(kUwThreads), 0, a.st, a.off,
+                     (uint32_t)max_terms, a.dig, a.pts, a.T);
   uint32_t ev;
-  memcpy(&ev, ws->pinned, 4);
-  if (ev & 1u) {
-    set_error("msm_batch: base coordinate not reduced mod p");
-    return SV_ERR_ARG;
-  }
-  if (ev & 2u) {
-    set_error("msm_batch: scalar not reduced (>= r)");
-    return SV_ERR_ARG;
-  }
+  SV_TRY(copy_back(ws, b, &ev));
+  SV_TRY(batch_error(ev, 0));
   // the partial sums are canonical Montgomery XYZZ (host::Xyzz has the same bytes); U_k of window w
   // sits at exponent 5 w + k: one Horner over the 130 exponents per MSM, the MSMs on the host pool
-  const host::Xyzz* U = reinterpret_cast<const host::Xyzz*>(ws->pinned + t_off);
+  const host::Xyzz* U = reinterpret_cast<const host::Xyzz*>(ws->pinned + b.pin_back + kWindowsHostErrBytes);
   constexpr int kTop = kQW * kUPerWin - 1;
   host_parallel_for(count, 1, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; k++) {
@@ -1293,9 +1233,7 @@ int msm_batch_windows_host(const void* d_bases, const void* d_scalars, const uin
   return SV_OK;
 }
 
-}  // namespace sv
-
-namespace sv {
+// ---- Precomputed fixed bases
 
 size_t table_precomputed_rows_bytes(size_t n) { return n * (size_t)kFixW * sizeof(G1Aff); }
 
@@ -1323,27 +1261,17 @@ int msm_batch_fixed_device(const void* d_pre, size_t rows, const uint32_t* d_bid
   if (!lease.ok()) return SV_ERR_DEVICE;
   Workspace* ws = lease.get();
   hipStream_t st = ws->stream;
-  SV_TRY(ws->reserve(Workspace::aligned(4)));
-  SV_TRY(ws->reserve_pinned(256));
-  uint32_t* err = ws->carve<uint32_t>(1);
+  const BatchBuffers b = batch_fixed_buffers();
+  SV_TRY(ws->reserve(b.ws.total));
+  SV_TRY(ws->reserve_pinned(b.pin.total));
+  uint32_t* err = buf_at<uint32_t>(ws->buf, b.flags);
   SV_HIP(hipMemsetAsync(err, 0, 4, st));
   hipLaunchKernelGGL(k_msm_batch_fixed, dim3((uint32_t)count), dim3(kThreads), 0, st, static_cast<const G1Aff*>(d_pre),
                      (uint32_t)rows, d_bidx, static_cast<const Fr*>(d_scalars), d_offsets,
                      form == SV_MONTGOMERY ? 1 : 0, static_cast<G1Aff*>(d_out), err);
-  SV_HIP(hipGetLastError());
-  SV_HIP(hipMemcpyAsync(ws->pinned, err, 4, hipMemcpyDeviceToHost, st));
-  SV_HIP(hipStreamSynchronize(st));
   uint32_t ev;
-  memcpy(&ev, ws->pinned, 4);
-  if (ev & 2u) {
-    set_error("msm_batch: scalar not reduced (>= r)");
-    return SV_ERR_ARG;
-  }
-  if (ev & 4u) {
-    set_error("msm_batch: base index out of the table (>= %zu)", rows);
-    return SV_ERR_ARG;
-  }
-  return SV_OK;
+  SV_TRY(copy_back(ws, b, &ev));
+  return batch_error(ev, rows);
 }
 
 }  // namespace sv

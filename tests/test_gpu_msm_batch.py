@@ -282,3 +282,54 @@ def test_device_small_batch_host_horner(gpu, oracle_cpp, monkeypatch, host_max, 
         torch.cuda.synchronize()
         got = [enc.g1_from_limbs(r, f) for r in out.cpu().numpy().view(np.uint64)]
         assert got == exp, sizes
+
+
+_P_LIMBS = [(b.P >> (64 * i)) & 0xffffffffffffffff for i in range(4)]
+_R_LIMBS = [(b.R >> (64 * i)) & 0xffffffffffffffff for i in range(4)]
+_HOST_MAX_0 = {"SVGPU_BATCH_HOST_MAX": "0"}
+_ERROR_ROUTES = {                                          # route: (switches, MSM sizes)
+    "host_horner": ({}, [3, 3]),
+    "fused": (_HOST_MAX_0, [3, 3]),
+    "bucket_pair": ({**_HOST_MAX_0, "SVGPU_BATCH_FUSE": "0"}, [3, 3]),
+    "quad_windows": ({**_HOST_MAX_0, "SVGPU_BATCH_BUCKETS": "0"}, [3, 3]),
+    "lane_windows_8": ({}, [257, 1]),
+}
+
+
+@pytest.mark.parametrize("route", [*_ERROR_ROUTES, "indexed", "fixed_table"])
+def test_error_messages_per_route(gpu, oracle_cpp, monkeypatch, route):
+    """The text of every argument error the batch drivers decode from the device's error word, on
+    each route of msm_batch_device (device buffers, canonical form): one scalar = r, and separately
+    one base coordinate = p.  The indexed route and the fixed table, over 4 rows: an index equal to
+    the row count."""
+    import svgpu
+    from svgpu import device as dv
+
+    def dev(a, dtype=np.int64):
+        return torch.from_numpy(a.view(dtype)).to(gpu)
+
+    if route in _ERROR_ROUTES:
+        env, sizes = _ERROR_ROUTES[route]
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        B, S, off = _ragged(oracle_cpp, sizes, 8100)
+        od = torch.tensor(off, dtype=torch.int64, device=gpu)
+        Sbad, Bbad = S.copy(), B.copy()
+        Sbad[1] = _R_LIMBS
+        Bbad[1, 0:4] = _P_LIMBS
+        with pytest.raises(svgpu.ArgumentError, match=r"scalar not reduced \(>= r\)"):
+            dv.msm_batch(dev(B), dev(Sbad), od, max(sizes), svgpu.SV_CANONICAL)
+        with pytest.raises(svgpu.ArgumentError, match=r"base coordinate not reduced mod p"):
+            dv.msm_batch(dev(Bbad), dev(S), od, max(sizes), svgpu.SV_CANONICAL)
+        return
+    rows, sizes = 4, [3, 3]
+    T, S, off = _ragged(oracle_cpp, [rows], 8200)[0], *_ragged(oracle_cpp, sizes, 8300)[1:]
+    od = torch.tensor(off, dtype=torch.int64, device=gpu)
+    idx = np.array([0, 1, 2, 3, rows, 1], np.int32)      # term 4: one past the last row
+    with pytest.raises(svgpu.ArgumentError, match=r"base index out of the table \(>= 4\)"):
+        if route == "indexed":
+            dv.msm_batch_indexed(dev(T), dev(idx, np.int32), dev(S), od, max(sizes), svgpu.SV_CANONICAL,
+                                 svgpu.SV_CANONICAL)
+        else:
+            with svgpu.BaseTable(T) as tab:
+                tab.msm_batch_device(dev(idx, np.int32), dev(S), od, svgpu.SV_CANONICAL)
