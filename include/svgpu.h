@@ -426,6 +426,61 @@ int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size
                            int direction, const sv_fe* shift, int form, int device,
                            void* stream) SV_NOEXCEPT;
 
+/* ---- running products and batch inversion over Fr columns in HBM -----------------------
+ * The running-product columns of a halo2 prover: the permutation argument's z (one per chunk of
+ * columns) and each lookup's z, which satisfy the relations the verifier checks in
+ * snark-verifier/src/system/halo2.rs:501-591 (permutation) and :593-660 (lookup),
+ *   z(wX) prod_j (v_j + beta sigma_j + gamma)  =  z(X) prod_j (v_j + beta delta^j X + gamma)
+ *   z(wX) (a' + beta)(s' + gamma)              =  z(X) (a + beta)(s + gamma),
+ * for columns that are already on the device (csrc/grand_product.hip: two product scans and ONE
+ * field inversion per call, three launches).
+ * fr_grand_product_device: with num(u) = prod_{j < n_num} num[j](u) and den(u) likewise, where a
+ *   factor's value at row u is x[u] + c (PLAIN), x[u] + s y[u] + c (COLUMN) or x[u] + s omega^u + c
+ *   (IDENTITY),
+ *     d_z[0] = z0,   d_z[i] = z0 prod_{u < i} num(u) / den(u)   for i < n,
+ *   and *out_total (a host pointer, may be NULL) the same with u < n: the value a prover checks
+ *   against 1, or seeds the next chunk's z0 with.  The descriptor arrays are host memory; d_x and
+ *   d_y point at n elements in HBM on `device`.  `form` covers the columns, s, c, z0, omega, d_z and
+ *   out_total.  omega is read only when a factor is IDENTITY and is then required: the caller passes
+ *   the domain's root_of_unity(k); s lets the caller pass beta delta^j ready-made, so the library
+ *   holds no delta.  The s of a PLAIN factor and the d_y of any factor but COLUMN are not read.  n
+ *   need not be a power of two.  n_den == 0 is a plain prefix product and runs no inversion; n_num
+ *   == 0 is legal too.  A row whose denominator is zero contributes the ratio 0 / 1: every later z
+ *   and the total are 0, which is what halo2's batch inversion gives (it leaves a zero "inverse"
+ *   zero).  All mod r: every output is determined bit for bit.
+ * fr_batch_invert_device: d_out[i] = 1 / d_in[i], and 0 where d_in[i] == 0 (halo2's batch
+ *   inversion, and ScalarLoader::batch_invert's unwrap_or_else, snark-verifier/src/loader.rs:241-247).
+ *   d_out == d_in is in place; any other overlap is SV_ERR_ARG ("overlaps").
+ * Checked before any device work, in this order (a side's descriptors beyond the first
+ * SV_PRODUCT_FACTORS_MAX are not looked at):
+ *   1. bad form; a null d_z, z0, descriptor array with a non-zero count, d_x, or d_y of a COLUMN
+ *      factor; a kind that is none of the three; a column or d_z not 16-byte aligned   SV_ERR_ARG
+ *   2. n == 0, or n_num + n_den == 0                                                   SV_ERR_EMPTY
+ *   3. n > 2^26, or a count above SV_PRODUCT_FACTORS_MAX                               SV_ERR_LEN
+ *   4. z0, an s or c that is read, or omega (when read) not below r   SV_ERR_ARG ("not reduced")
+ *   5. an IDENTITY factor with omega == NULL                                           SV_ERR_ARG
+ *   6. d_z overlapping any column                                       SV_ERR_ARG ("overlaps")
+ * (batch inversion: bad form, null, alignment; n == 0; n > 2^26; the partial overlap).  An element
+ * not below r is found on the device and is SV_ERR_ARG ("not reduced") for that call: d_z (d_out) is
+ * then unspecified, nothing outside it is written, and the next call is exact.  Points 1 and 2 of
+ * "Streams" apply (ordered after `stream`, synchronous); re-entrant from any number of threads.
+ * A grand product holds its rows' two products in pooled scratch between its first and its last
+ * launch: 64 B per row (4 GiB at n = 2^26), so the columns are read once; batch inversion holds
+ * nothing per row.
+ * Not covered: several z columns in one call; the permuted columns of a lookup (a sort); host
+ * buffers; multi-device columns.                                                              */
+enum { SV_FACTOR_PLAIN = 0,      /* f[i] = x[i] + c              */
+       SV_FACTOR_COLUMN = 1,     /* f[i] = x[i] + s*y[i] + c     */
+       SV_FACTOR_IDENTITY = 2 }; /* f[i] = x[i] + s*omega^i + c  */
+typedef struct { const sv_fe* d_x; const sv_fe* d_y; sv_fe s; sv_fe c; uint32_t kind; } sv_fr_factor;
+#define SV_PRODUCT_FACTORS_MAX 16   /* per side */
+int sv_bn254_fr_grand_product_device(const sv_fr_factor* num, size_t n_num,
+                                     const sv_fr_factor* den, size_t n_den, size_t n,
+                                     const sv_fe* z0, const sv_fe* omega, int form, sv_fe* d_z,
+                                     sv_fe* out_total, int device, void* stream) SV_NOEXCEPT;
+int sv_bn254_fr_batch_invert_device(const sv_fe* d_in, sv_fe* d_out, size_t n, int form,
+                                    int device, void* stream) SV_NOEXCEPT;
+
 /* ---- Poseidon sponge over BN254 Fr --------------------------
  * x^5 HADES permutation, width t = 3 (R_F 8, R_P 57, rate 2: the SDK's PoseidonTranscript,
  * snark-verifier-sdk/src/halo2.rs:52-71) or t = 5 (R_F 8, R_P 60, rate 4).  States are t

@@ -18,6 +18,7 @@
 #include "codec.hpp"
 #include "decider.hpp"
 #include "gen.hpp"
+#include "grand_product.hpp"
 #include "host_ec.hpp"
 #include "host_poseidon.hpp"
 #include "kzg_open.hpp"
@@ -1981,6 +1982,174 @@ int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size
     return SV_ERR_ARG;
   }
   return SV_OK;
+  SV_GUARD_END
+}
+
+// ---- running products and batch inversion over Fr columns (csrc/grand_product.hip) ----
+namespace {
+bool fr_reduced(const sv_fe& a) { return host::f_is_reduced(fe_in(a), host::R64); }
+
+// rule 1 for one side: the array, then per descriptor the kind, the pointers and their alignment
+int factor_pointer_rules(const sv_fr_factor* f, size_t count, const char* side) {
+  if (count && !f) {
+    sv::set_error("null pointer (%s descriptors)", side);
+    return SV_ERR_ARG;
+  }
+  for (size_t j = 0; j < std::min(count, (size_t)SV_PRODUCT_FACTORS_MAX); j++) {
+    if (f[j].kind != SV_FACTOR_PLAIN && f[j].kind != SV_FACTOR_COLUMN && f[j].kind != SV_FACTOR_IDENTITY) {
+      sv::set_error("%s factor %zu: kind %u is none of SV_FACTOR_PLAIN, _COLUMN, _IDENTITY", side, j, f[j].kind);
+      return SV_ERR_ARG;
+    }
+    const bool column = f[j].kind == SV_FACTOR_COLUMN;
+    if (!f[j].d_x || (column && !f[j].d_y)) {
+      sv::set_error("null pointer (%s factor %zu)", side, j);
+      return SV_ERR_ARG;
+    }
+    if (((uintptr_t)f[j].d_x | (column ? (uintptr_t)f[j].d_y : 0)) & 15u) {
+      sv::set_error("%s factor %zu: columns must be 16-byte aligned", side, j);
+      return SV_ERR_ARG;
+    }
+  }
+  return SV_OK;
+}
+
+// rule 4 for one side: the s and c that the kernels read
+int factor_scalar_rules(const sv_fr_factor* f, size_t count, const char* side) {
+  for (size_t j = 0; j < count; j++)
+    if (!fr_reduced(f[j].c) || (f[j].kind != SV_FACTOR_PLAIN && !fr_reduced(f[j].s))) {
+      sv::set_error("%s factor %zu: s or c not reduced mod the scalar field order", side, j);
+      return SV_ERR_ARG;
+    }
+  return SV_OK;
+}
+
+bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
+
+// both entry points past their checks: the lease, the three launches, the head
+int grand_product_run(const GpCall& call, int device, void* stream, sv_fe* out_total) {
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  SV_TRY(ws->reserve(grand_product_scratch_bytes(call.n, call.invert)));
+  SV_TRY(ws->reserve_pinned(kGpHeadBytes));
+  SV_TRY(grand_product_enqueue(call, ws->buf, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned, ws->buf, kGpHeadBytes, hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl.armed = false;
+  uint32_t errv;
+  memcpy(&errv, ws->pinned + kGpErrOffset, sizeof errv);
+  if (errv) {
+    sv::set_error("invalid input: element not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  if (out_total) memcpy(out_total->l, ws->pinned + kGpTotalOffset, sizeof(sv_fe));
+  return SV_OK;
+}
+}  // namespace
+
+int sv_bn254_fr_grand_product_device(const sv_fr_factor* num, size_t n_num, const sv_fr_factor* den, size_t n_den,
+                                     size_t n, const sv_fe* z0, const sv_fe* omega, int form, sv_fe* d_z,
+                                     sv_fe* out_total, int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_z || !z0) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  SV_TRY(factor_pointer_rules(num, n_num, "numerator"));
+  SV_TRY(factor_pointer_rules(den, n_den, "denominator"));
+  if ((uintptr_t)d_z & 15u) {
+    sv::set_error("d_z must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (n == 0 || (n_num == 0 && n_den == 0)) {
+    sv::set_error("the product should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (n > kGpMaxRows) {
+    sv::set_error("n = %zu exceeds the per-device limit 2^26", n);
+    return SV_ERR_LEN;
+  }
+  if (n_num > SV_PRODUCT_FACTORS_MAX || n_den > SV_PRODUCT_FACTORS_MAX) {
+    sv::set_error("%zu + %zu factors: a side takes at most %d", n_num, n_den, SV_PRODUCT_FACTORS_MAX);
+    return SV_ERR_LEN;
+  }
+  if (!fr_reduced(*z0)) {
+    sv::set_error("z0 not reduced mod the scalar field order");
+    return SV_ERR_ARG;
+  }
+  SV_TRY(factor_scalar_rules(num, n_num, "numerator"));
+  SV_TRY(factor_scalar_rules(den, n_den, "denominator"));
+  bool identity = false;
+  for (size_t j = 0; j < n_num + n_den; j++)
+    identity |= (j < n_num ? num[j] : den[j - n_num]).kind == SV_FACTOR_IDENTITY;
+  if (identity && omega && !fr_reduced(*omega)) {
+    sv::set_error("omega not reduced mod the scalar field order");
+    return SV_ERR_ARG;
+  }
+  if (identity && !omega) {
+    sv::set_error("null pointer (omega: a factor is SV_FACTOR_IDENTITY)");
+    return SV_ERR_ARG;
+  }
+  for (size_t j = 0; j < n_num + n_den; j++) {
+    const sv_fr_factor& f = j < n_num ? num[j] : den[j - n_num];
+    if (ranges_overlap(d_z, f.d_x, n * sizeof(sv_fe)) ||
+        (f.kind == SV_FACTOR_COLUMN && ranges_overlap(d_z, f.d_y, n * sizeof(sv_fe)))) {
+      sv::set_error("d_z overlaps a column (the last launch reads the columns again while it writes)");
+      return SV_ERR_ARG;
+    }
+  }
+  GpCall call{};
+  call.num = num, call.n_num = n_num;
+  call.den = den, call.n_den = n_den;
+  call.n = n;
+  call.z0 = *z0;
+  call.omega = omega;
+  call.form = form;
+  call.invert = false;
+  call.d_out = d_z;
+  return grand_product_run(call, device, stream, out_total);
+  SV_GUARD_END
+}
+
+int sv_bn254_fr_batch_invert_device(const sv_fe* d_in, sv_fe* d_out, size_t n, int form, int device,
+                                    void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_in || !d_out) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15u) {
+    sv::set_error("d_in and d_out must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (n == 0) {
+    sv::set_error("the column should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (n > kGpMaxRows) {
+    sv::set_error("n = %zu exceeds the per-device limit 2^26", n);
+    return SV_ERR_LEN;
+  }
+  if (d_in != d_out && ranges_overlap(d_in, d_out, n * sizeof(sv_fe))) {
+    sv::set_error("d_out overlaps d_in without being d_in (in place is d_out == d_in)");
+    return SV_ERR_ARG;
+  }
+  sv_fr_factor column{};
+  column.d_x = d_in;
+  column.kind = SV_FACTOR_PLAIN;
+  GpCall call{};
+  call.num = &column, call.n_num = 1;
+  call.n = n;
+  call.form = form;
+  call.invert = true;
+  call.d_out = d_out;
+  return grand_product_run(call, device, stream, nullptr);
   SV_GUARD_END
 }
 

@@ -66,5 +66,54 @@ def ntt_device(data, **kwargs):
     return run(data, **kwargs)
 
 
+def grand_product_device(num, den, **kwargs):
+    """svgpu.device.grand_product_device (imported on first use: that module needs torch)."""
+    from .device import grand_product_device as run
+    return run(num, den, **kwargs)
+
+
+def batch_invert_device(data, **kwargs):
+    """svgpu.device.batch_invert_device (imported on first use: that module needs torch)."""
+    from .device import batch_invert_device as run
+    return run(data, **kwargs)
+
+
+def permutation_factors(values, sigmas, beta, gamma, delta_powers):
+    """The factor lists (num, den) of one chunk of the permutation argument (system/halo2.rs:501-591):
+    z(wX) prod_j (v_j + beta sigma_j + gamma) = z(X) prod_j (v_j + beta delta^j X + gamma), so row i
+    multiplies z by prod_j (v_j + beta delta^j omega^i + gamma) / prod_j (v_j + beta sigma_j + gamma).
+    delta_powers[j] is the delta^j of the chunk's j-th column; scalars are canonical ints."""
+    from ._lib import SV_FACTOR_COLUMN, SV_FACTOR_IDENTITY
+    from .encoding import R
+    if not len(values) == len(sigmas) == len(delta_powers):
+        raise LengthError("permutation_product: values, sigmas and delta_powers differ in length")
+    num = [(SV_FACTOR_IDENTITY, v, None, beta * d % R, gamma) for v, d in zip(values, delta_powers)]
+    den = [(SV_FACTOR_COLUMN, v, s, beta % R, gamma) for v, s in zip(values, sigmas)]
+    return num, den
+
+
+def lookup_factors(inputs, tables, permuted_input, permuted_table, beta, gamma):
+    """The factor lists (num, den) of one lookup argument (system/halo2.rs:593-660):
+    z(wX) (a' + beta)(s' + gamma) = z(X) (a + beta)(s + gamma) with a = inputs, s = tables (the
+    compressed expressions) and a', s' their permuted columns."""
+    from ._lib import SV_FACTOR_PLAIN
+    num = [(SV_FACTOR_PLAIN, inputs, None, 0, beta), (SV_FACTOR_PLAIN, tables, None, 0, gamma)]
+    den = [(SV_FACTOR_PLAIN, permuted_input, None, 0, beta), (SV_FACTOR_PLAIN, permuted_table, None, 0, gamma)]
+    return num, den
+
+
+def permutation_product(values, sigmas, beta, gamma, delta_powers, omega, z0=1, **kwargs):
+    """grand_product_device over permutation_factors(...): (z, total) of one chunk; the next chunk
+    takes this total as its z0."""
+    num, den = permutation_factors(values, sigmas, beta, gamma, delta_powers)
+    return grand_product_device(num, den, z0=z0, omega=omega, **kwargs)
+
+
+def lookup_product(inputs, tables, permuted_input, permuted_table, beta, gamma, z0=1, **kwargs):
+    """grand_product_device over lookup_factors(...): (z, total) of one lookup."""
+    num, den = lookup_factors(inputs, tables, permuted_input, permuted_table, beta, gamma)
+    return grand_product_device(num, den, z0=z0, **kwargs)
+
+
 def version() -> str:
     return lib.sv_version().decode()

@@ -25,6 +25,11 @@ SV_NTT_MAX_LOG = 26        # log2 of the longest transform
 SV_NTT_FORWARD = 0
 SV_NTT_INVERSE = 1
 
+SV_FACTOR_PLAIN = 0        # f[i] = x[i] + c
+SV_FACTOR_COLUMN = 1       # f[i] = x[i] + s*y[i] + c
+SV_FACTOR_IDENTITY = 2     # f[i] = x[i] + s*omega^i + c
+SV_PRODUCT_FACTORS_MAX = 16  # factors per side of a grand product
+
 SV_ENC_HALO2_COMPRESSED = 0
 SV_ENC_EVM = 1
 
@@ -83,6 +88,10 @@ class sv_fq12(Structure):
 class sv_shplonk_set(Structure):
     _fields_ = [("first_poly", c_uint32), ("num_polys", c_uint32), ("first_point", c_uint32),
                 ("num_points", c_uint32)]
+
+
+class sv_fr_factor(Structure):
+    _fields_ = [("d_x", c_void_p), ("d_y", c_void_p), ("s", sv_fe), ("c", sv_fe), ("kind", c_uint32)]
 
 
 class sv_msm_stats(Structure):
@@ -154,6 +163,9 @@ PROTOTYPES = [
     ("sv_bn254_fr_root_of_unity", c_int, [c_uint32, c_int, POINTER(sv_fe)]),
     ("sv_bn254_fr_ntt_device", c_int, [c_void_p, c_void_p, c_uint32, c_size_t, c_int, c_void_p, c_int, c_int,
                                         c_void_p]),
+    ("sv_bn254_fr_grand_product_device", c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, POINTER(sv_fe),
+                                                  POINTER(sv_fe), c_int, c_void_p, POINTER(sv_fe), c_int, c_void_p]),
+    ("sv_bn254_fr_batch_invert_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_permute", c_int, [c_void_p, c_size_t, c_int, c_int]),
     ("sv_bn254_poseidon_permute_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_squeeze", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import copy
 import ctypes
+from collections import namedtuple
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -222,6 +223,85 @@ def ntt_device(data: torch.Tensor, inverse: bool = False, shift: Optional[int] =
                                                ctypes.byref(gs) if gs is not None else None, form, d,
                                                _stream_handle(data.device)),
                "sv_bn254_fr_ntt_device")
+    return out
+
+
+# One factor of a grand product: kind (SV_FACTOR_*), x and -- COLUMN -- y as (n, 4) int64 tensors of
+# limbs, s and c as canonical ints.  A plain tuple of the same fields, shorter where the rest is
+# the default, does as well.
+Factor = namedtuple("Factor", "kind x y s c", defaults=(None, 0, 0))
+
+
+def _column(t: torch.Tensor, n: int, dev, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 4:
+        raise _lib.ArgumentError(f"grand_product: {what} is an (n, 4) int64 tensor of limbs")
+    if t.device != dev:
+        raise _lib.ArgumentError("grand_product: the columns of a call live on one device")
+    if t.shape[0] != n:
+        raise _lib.LengthError(f"grand_product: {what} has {t.shape[0]} rows, the call {n}")
+    return t.contiguous()
+
+
+def factor_array(factors, form: int, n: int, dev, keep: list):
+    """The host descriptor array (at least one element) of one side; the contiguous tensors it
+    points into are appended to `keep`."""
+    arr = (_lib.sv_fr_factor * max(len(factors), 1))()
+    for j, f in enumerate(factors):
+        f = Factor(*f)
+        x = _column(f.x, n, dev, "x")
+        keep.append(x)
+        arr[j].d_x, arr[j].kind = x.data_ptr(), f.kind
+        if f.kind == _lib.SV_FACTOR_COLUMN:
+            y = _column(f.y, n, dev, "y")
+            keep.append(y)
+            arr[j].d_y = y.data_ptr()
+        arr[j].s, arr[j].c = enc.fr_struct(f.s, form), enc.fr_struct(f.c, form)
+    return arr
+
+
+def grand_product_device(num, den, z0: int = 1, omega: Optional[int] = None, form: int = _lib.SV_MONTGOMERY,
+                         out: torch.Tensor = None) -> Tuple[torch.Tensor, int]:
+    """The running product z[0] = z0, z[i + 1] = z[i] prod_j num_j(i) / prod_j den_j(i) over HBM-resident
+    columns ((n, 4) int64 limbs in `form`) -> (z as n rows in `form`, the total z0 prod_{i < n} as a
+    canonical int).  num and den are lists of Factor (or tuples); z0, s, c and omega are canonical
+    ints; omega = root_of_unity(k) is needed when a factor is SV_FACTOR_IDENTITY.  A row whose
+    denominator is zero leaves every later z and the total zero.  `out` (n rows) must not overlap a
+    column."""
+    num, den = [Factor(*f) for f in num], [Factor(*f) for f in den]
+    if not num and not den:
+        raise _lib.EmptyError("grand_product: no factors")
+    first = (num + den)[0].x
+    d, dev, n = _dev_index(first), first.device, first.shape[0]
+    keep: list = []
+    na, da = factor_array(num, form, n, dev, keep), factor_array(den, form, n, dev, keep)
+    if out is None:
+        out = torch.empty((max(n, 1), 4), dtype=torch.int64, device=dev)
+    elif (out.device != dev or out.dtype != torch.int64 or not out.is_contiguous() or out.dim() != 2
+          or out.shape[1] != 4 or out.shape[0] != n):
+        raise _lib.LengthError(f"grand_product: out must be a contiguous ({n}, 4) int64 tensor on {dev}")
+    zs, total = enc.fr_struct(z0, form), _lib.sv_fe()
+    ws = enc.fr_struct(omega, form) if omega is not None else None
+    _lib.check(_lib.lib.sv_bn254_fr_grand_product_device(na, len(num), da, len(den), n, ctypes.byref(zs),
+                                                         ctypes.byref(ws) if ws is not None else None, form,
+                                                         out.data_ptr(), ctypes.byref(total), d, _stream_handle(dev)),
+               "sv_bn254_fr_grand_product_device")
+    return out[:n], enc.fr_from_struct(total, form)
+
+
+def batch_invert_device(data: torch.Tensor, form: int = _lib.SV_MONTGOMERY, out: torch.Tensor = None) -> torch.Tensor:
+    """1 / x for every row of an HBM-resident column ((n, 4) int64 limbs in `form`), 0 where x is 0.
+    out=None allocates, out=data is in place; any other `out` (n rows) must not overlap data."""
+    d = _dev_index(data)
+    if data.dtype != torch.int64 or data.dim() != 2 or data.shape[1] != 4 or not data.is_contiguous():
+        raise _lib.ArgumentError("batch_invert: data is a contiguous (n, 4) int64 tensor of limbs")
+    if out is None:
+        out = torch.empty_like(data)
+    elif (out.device != data.device or out.dtype != torch.int64 or not out.is_contiguous()
+          or out.shape != data.shape):
+        raise _lib.LengthError(f"batch_invert: out must be a contiguous {tuple(data.shape)} int64 tensor on {data.device}")
+    _lib.check(_lib.lib.sv_bn254_fr_batch_invert_device(data.data_ptr(), out.data_ptr(), data.shape[0], form, d,
+                                                        _stream_handle(data.device)),
+               "sv_bn254_fr_batch_invert_device")
     return out
 
 

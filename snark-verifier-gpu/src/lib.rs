@@ -92,6 +92,21 @@ pub const SV_EVAL_POINTS_MAX: usize = 16;
 pub const SV_NTT_MAX_LOG: u32 = 26;
 pub const SV_NTT_FORWARD: c_int = 0;
 pub const SV_NTT_INVERSE: c_int = 1;
+/// sv_fr_factor: one factor of a grand product; `kind` is one of the SV_FACTOR_* values.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SvFrFactor {
+    pub d_x: *const SvFe,
+    pub d_y: *const SvFe,
+    pub s: SvFe,
+    pub c: SvFe,
+    pub kind: u32,
+}
+pub const SV_FACTOR_PLAIN: u32 = 0;
+pub const SV_FACTOR_COLUMN: u32 = 1;
+pub const SV_FACTOR_IDENTITY: u32 = 2;
+/// Factors per side of sv_bn254_fr_grand_product_device.
+pub const SV_PRODUCT_FACTORS_MAX: usize = 16;
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct SvMsmStats {
@@ -195,6 +210,15 @@ extern "C" {
     pub fn sv_bn254_fr_ntt_device(d_in: *const SvFe, d_out: *mut SvFe, log_n: u32, count: usize,
                                   direction: c_int, shift: *const SvFe, form: c_int, device: c_int,
                                   stream: *mut c_void) -> c_int;
+    /// Running product z[0] = z0, z[i + 1] = z[i] num(i) / den(i) over columns in HBM; descriptor arrays
+    /// and z0 / omega / out_total are host pointers (omega, out_total may be null).
+    pub fn sv_bn254_fr_grand_product_device(num: *const SvFrFactor, n_num: usize, den: *const SvFrFactor,
+                                            n_den: usize, n: usize, z0: *const SvFe, omega: *const SvFe,
+                                            form: c_int, d_z: *mut SvFe, out_total: *mut SvFe, device: c_int,
+                                            stream: *mut c_void) -> c_int;
+    /// d_out[i] = 1 / d_in[i], 0 where d_in[i] is 0; d_out == d_in is in place.
+    pub fn sv_bn254_fr_batch_invert_device(d_in: *const SvFe, d_out: *mut SvFe, n: usize, form: c_int,
+                                           device: c_int, stream: *mut c_void) -> c_int;
     pub fn sv_bn254_shplonk_work_elems(n_sets: usize, n: usize, elems: *mut u64) -> c_int;
     pub fn sv_bn254_shplonk_quotient_device(handle: u64, offset: usize, d_polys: *const *const SvFe,
                                             lens: *const u64, m: usize, sets: *const SvShplonkSet, n_sets: usize,
