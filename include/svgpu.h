@@ -467,8 +467,8 @@ int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size
  * A grand product holds its rows' two products in pooled scratch between its first and its last
  * launch: 64 B per row (4 GiB at n = 2^26), so the columns are read once; batch inversion holds
  * nothing per row.
- * Not covered: several z columns in one call; the permuted columns of a lookup (a sort); host
- * buffers; multi-device columns.                                                              */
+ * Not covered: several z columns in one call; host buffers; multi-device columns (a lookup's
+ * permuted columns: the next block).                                                          */
 enum { SV_FACTOR_PLAIN = 0,      /* f[i] = x[i] + c              */
        SV_FACTOR_COLUMN = 1,     /* f[i] = x[i] + s*y[i] + c     */
        SV_FACTOR_IDENTITY = 2 }; /* f[i] = x[i] + s*omega^i + c  */
@@ -480,6 +480,51 @@ int sv_bn254_fr_grand_product_device(const sv_fr_factor* num, size_t n_num,
                                      sv_fe* out_total, int device, void* stream) SV_NOEXCEPT;
 int sv_bn254_fr_batch_invert_device(const sv_fe* d_in, sv_fe* d_out, size_t n, int form,
                                     int device, void* stream) SV_NOEXCEPT;
+
+/* ---- Fr sort and the permuted columns of a lookup in HBM ---------------------------------
+ * The a' and s' that the lookup relation above reads, from the compressed input expression A and
+ * table expression S of a lookup, for columns that are already on the device
+ * (csrc/lookup_permute.hip: a least-significant-digit radix sort over the canonical 256-bit value
+ * in 8-bit digits, dead digits skipped, and a lower bound plus two scans).  Order is by canonical
+ * integer value in [0, r) -- what Ord on halo2curves' Fr compares -- whatever `form` the data is in.
+ * fr_sort_device: d_out = d_in sorted ascending (stable, though equal elements cannot be told
+ *   apart), in `form`.  d_out == d_in is in place; any other overlap is SV_ERR_ARG ("overlaps").
+ *   n need not be a power of two.
+ * fr_lookup_permute_device: halo2's permute_expression_pair (halo2_proofs
+ *   src/plonk/lookup/prover.rs) over n usable rows; the blinding rows after them are the caller's
+ *   and are never touched.
+ *     1. A' = A sorted ascending.  Row i of A' is a leader if i == 0 or A'[i] != A'[i-1], otherwise a
+ *        repeat.
+ *     2. Every leader's value must occur in S; S'[i] = A'[i] at every leader.
+ *     3. L[0..m) = S with one copy of each distinct value of A removed, ascending with multiplicity
+ *        (m = the number of repeats); the repeats r_0 < .. < r_{m-1} take S'[r_k] = L[m-1-k]: the
+ *        smallest leftover goes to the LAST repeated row, as halo2's pop() does.
+ *   The output satisfies a'[0] = s'[0], a'[i] = s'[i] or a'[i] = a'[i-1] on every row, and
+ *   prod (a + beta)(s + gamma) = prod (a' + beta)(s' + gamma), bit for bit as halo2 arranges it.
+ *   The inputs are only read.  Any overlap between an output and an input, or between the two
+ *   outputs, is SV_ERR_ARG ("overlaps").  A leader whose value is not in S: SV_ERR_ARG ("not in
+ *   table") and *out_missing_row = the SMALLEST such row of A' (where halo2 returns
+ *   ConstraintSystemFailure); out_missing_row is a host pointer, may be NULL, and is UINT64_MAX on
+ *   success.  The outputs are unspecified after a failure.
+ * Checked before any device work, in this order:
+ *   1. bad form; a null column; a pointer not 16-byte aligned                          SV_ERR_ARG
+ *   2. n == 0                                                                          SV_ERR_EMPTY
+ *   3. n > 2^26                                                                        SV_ERR_LEN
+ *   4. the overlaps above                                               SV_ERR_ARG ("overlaps")
+ * An element not below r is found on the device and is SV_ERR_ARG ("not reduced") for that call
+ * (it wins over a missing value): the outputs are then unspecified, nothing outside them is
+ * written, and the next call is exact.  Points 1 and 2 of "Streams" apply (ordered after `stream`,
+ * synchronous); re-entrant from any number of threads.  Pooled scratch per row: 65 B for a sort
+ * (two canonical images and the per-block digit counts), 145 B for a permutation (four images, four
+ * u32 lists, the counts): 9.1 GiB at n = 2^26.
+ * Not covered: the theta-compression of several columns into A and S; the blinding rows; host
+ * buffers; multi-device columns.                                                              */
+int sv_bn254_fr_sort_device(const sv_fe* d_in, sv_fe* d_out, size_t n, int form, int device,
+                            void* stream) SV_NOEXCEPT;
+int sv_bn254_fr_lookup_permute_device(const sv_fe* d_input, const sv_fe* d_table, size_t n,
+                                      int form, sv_fe* d_permuted_input, sv_fe* d_permuted_table,
+                                      uint64_t* out_missing_row, int device,
+                                      void* stream) SV_NOEXCEPT;
 
 /* ---- Poseidon sponge over BN254 Fr --------------------------
  * x^5 HADES permutation, width t = 3 (R_F 8, R_P 57, rate 2: the SDK's PoseidonTranscript,

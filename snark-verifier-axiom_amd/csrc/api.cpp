@@ -22,6 +22,7 @@
 #include "host_ec.hpp"
 #include "host_poseidon.hpp"
 #include "kzg_open.hpp"
+#include "lookup_permute.hpp"
 #include "msm.hpp"
 #include "msm_batch.hpp"
 #include "msm_batch_plan.hpp"
@@ -2150,6 +2151,114 @@ int sv_bn254_fr_batch_invert_device(const sv_fe* d_in, sv_fe* d_out, size_t n, i
   call.invert = true;
   call.d_out = d_out;
   return grand_product_run(call, device, stream, nullptr);
+  SV_GUARD_END
+}
+
+// ---- Fr sort and a lookup's permuted columns (csrc/lookup_permute.hip) ----
+namespace {
+// both entry points past their checks: the lease, the launches, the head
+int lookup_permute_run(const LpCall& call, int device, void* stream, uint64_t* out_missing_row) {
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  SV_TRY(ws->reserve(lookup_permute_scratch_bytes(call.n, call.permute)));
+  SV_TRY(ws->reserve_pinned(kLpHeadBytes));
+  SV_TRY(lookup_permute_enqueue(call, ws->buf, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned, ws->buf, kLpHeadBytes, hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl.armed = false;
+  uint32_t errv;
+  uint64_t missing;
+  memcpy(&errv, ws->pinned + kLpErrOffset, sizeof errv);
+  memcpy(&missing, ws->pinned + kLpMissingOffset, sizeof missing);
+  if (errv) {
+    sv::set_error("invalid input: element not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  if (out_missing_row) *out_missing_row = missing ? UINT64_MAX - missing : UINT64_MAX;
+  if (missing) {
+    sv::set_error("row %llu of the permuted input holds a value that is not in table",
+                  (unsigned long long)(UINT64_MAX - missing));
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+}  // namespace
+
+int sv_bn254_fr_sort_device(const sv_fe* d_in, sv_fe* d_out, size_t n, int form, int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_in || !d_out) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (((uintptr_t)d_in | (uintptr_t)d_out) & 15u) {
+    sv::set_error("d_in and d_out must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (n == 0) {
+    sv::set_error("the column should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (n > kLpMaxRows) {
+    sv::set_error("n = %zu exceeds the per-device limit 2^26", n);
+    return SV_ERR_LEN;
+  }
+  if (d_in != d_out && ranges_overlap(d_in, d_out, n * sizeof(sv_fe))) {
+    sv::set_error("d_out overlaps d_in without being d_in (in place is d_out == d_in)");
+    return SV_ERR_ARG;
+  }
+  LpCall call{};
+  call.d_in = d_in;
+  call.n = n;
+  call.form = form;
+  call.permute = false;
+  call.d_out = d_out;
+  return lookup_permute_run(call, device, stream, nullptr);
+  SV_GUARD_END
+}
+
+int sv_bn254_fr_lookup_permute_device(const sv_fe* d_input, const sv_fe* d_table, size_t n, int form,
+                                      sv_fe* d_permuted_input, sv_fe* d_permuted_table, uint64_t* out_missing_row,
+                                      int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_input || !d_table || !d_permuted_input || !d_permuted_table) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (((uintptr_t)d_input | (uintptr_t)d_table | (uintptr_t)d_permuted_input | (uintptr_t)d_permuted_table) & 15u) {
+    sv::set_error("the columns must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (n == 0) {
+    sv::set_error("the columns should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (n > kLpMaxRows) {
+    sv::set_error("n = %zu exceeds the per-device limit 2^26", n);
+    return SV_ERR_LEN;
+  }
+  const size_t bytes = n * sizeof(sv_fe);
+  if (ranges_overlap(d_permuted_input, d_input, bytes) || ranges_overlap(d_permuted_input, d_table, bytes) ||
+      ranges_overlap(d_permuted_table, d_input, bytes) || ranges_overlap(d_permuted_table, d_table, bytes)) {
+    sv::set_error("an output overlaps an input column (the inputs are only read)");
+    return SV_ERR_ARG;
+  }
+  if (ranges_overlap(d_permuted_input, d_permuted_table, bytes)) {
+    sv::set_error("d_permuted_table overlaps d_permuted_input");
+    return SV_ERR_ARG;
+  }
+  LpCall call{};
+  call.d_in = d_input;
+  call.d_table = d_table;
+  call.n = n;
+  call.form = form;
+  call.permute = true;
+  call.d_out = d_permuted_input;
+  call.d_out_table = d_permuted_table;
+  return lookup_permute_run(call, device, stream, out_missing_row);
   SV_GUARD_END
 }
 

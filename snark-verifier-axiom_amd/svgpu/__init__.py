@@ -115,5 +115,27 @@ def lookup_product(inputs, tables, permuted_input, permuted_table, beta, gamma, 
     return grand_product_device(num, den, z0=z0, **kwargs)
 
 
+def sort_device(data, **kwargs):
+    """svgpu.device.sort_device (imported on first use: that module needs torch)."""
+    from .device import sort_device as run
+    return run(data, **kwargs)
+
+
+def lookup_permute_device(inputs, tables, **kwargs):
+    """svgpu.device.lookup_permute_device (imported on first use: that module needs torch)."""
+    from .device import lookup_permute_device as run
+    return run(inputs, tables, **kwargs)
+
+
+def lookup_argument(inputs, tables, beta, gamma, z0=1, **kwargs):
+    """One lookup argument on columns in HBM: lookup_permute_device, then lookup_product over its
+    output -> (permuted_input, permuted_table, z, total).  For a lookup that holds, total == z0.
+    form= goes to both calls, out= (two tensors) to the permutation."""
+    out = kwargs.pop("out", None)
+    permuted_input, permuted_table = lookup_permute_device(inputs, tables, out=out, **kwargs)
+    z, total = lookup_product(inputs, tables, permuted_input, permuted_table, beta, gamma, z0=z0, **kwargs)
+    return permuted_input, permuted_table, z, total
+
+
 def version() -> str:
     return lib.sv_version().decode()

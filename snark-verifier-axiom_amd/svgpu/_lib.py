@@ -166,6 +166,9 @@ PROTOTYPES = [
     ("sv_bn254_fr_grand_product_device", c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, POINTER(sv_fe),
                                                   POINTER(sv_fe), c_int, c_void_p, POINTER(sv_fe), c_int, c_void_p]),
     ("sv_bn254_fr_batch_invert_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    ("sv_bn254_fr_sort_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    ("sv_bn254_fr_lookup_permute_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
+                                                   POINTER(c_uint64), c_int, c_void_p]),
     ("sv_bn254_poseidon_permute", c_int, [c_void_p, c_size_t, c_int, c_int]),
     ("sv_bn254_poseidon_permute_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_squeeze", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

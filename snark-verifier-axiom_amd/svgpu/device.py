@@ -305,6 +305,63 @@ def batch_invert_device(data: torch.Tensor, form: int = _lib.SV_MONTGOMERY, out:
     return out
 
 
+def _fr_column(t: torch.Tensor, what: str) -> None:
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 4
+            or not t.is_contiguous()):
+        raise _lib.ArgumentError(f"{what} is a contiguous (n, 4) int64 tensor of limbs")
+
+
+def sort_device(data: torch.Tensor, form: int = _lib.SV_MONTGOMERY, out: torch.Tensor = None) -> torch.Tensor:
+    """An HBM-resident column ((n, 4) int64 limbs in `form`) sorted ascending by canonical value, in
+    `form`.  out=None allocates, out=data is in place; any other `out` (n rows) must not overlap data."""
+    d = _dev_index(data)
+    _fr_column(data, "sort: data")
+    if out is None:
+        out = torch.empty_like(data)
+    elif (out.device != data.device or out.dtype != torch.int64 or not out.is_contiguous()
+          or out.shape != data.shape):
+        raise _lib.LengthError(f"sort: out must be a contiguous {tuple(data.shape)} int64 tensor on {data.device}")
+    _lib.check(_lib.lib.sv_bn254_fr_sort_device(data.data_ptr(), out.data_ptr(), data.shape[0], form, d,
+                                                _stream_handle(data.device)),
+               "sv_bn254_fr_sort_device")
+    return out
+
+
+def lookup_permute_device(inputs: torch.Tensor, tables: torch.Tensor, form: int = _lib.SV_MONTGOMERY,
+                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """halo2's permute_expression_pair over HBM-resident columns ((n, 4) int64 limbs in `form`): the
+    compressed input and table expressions of a lookup -> (permuted_input, permuted_table) in `form`.
+    n is the usable rows; the blinding rows are the caller's.  out=None allocates; out=(a', s') are
+    two n-row tensors that overlap neither each other nor an input.  An input value that is not in
+    the table raises ArgumentError ("not in table") whose .row is the smallest such row of the
+    permuted input."""
+    d = _dev_index(inputs)
+    _fr_column(inputs, "lookup_permute: inputs")
+    _fr_column(tables, "lookup_permute: tables")
+    if tables.device != inputs.device:
+        raise _lib.ArgumentError("lookup_permute: the columns of a call live on one device")
+    if tables.shape != inputs.shape:
+        raise _lib.LengthError(f"lookup_permute: tables has {tables.shape[0]} rows, inputs {inputs.shape[0]}")
+    if out is None:
+        out = (torch.empty_like(inputs), torch.empty_like(inputs))
+    for o in out:
+        if (not isinstance(o, torch.Tensor) or o.device != inputs.device or o.dtype != torch.int64
+                or not o.is_contiguous() or o.shape != inputs.shape):
+            raise _lib.LengthError(f"lookup_permute: out is two contiguous {tuple(inputs.shape)} int64 tensors on "
+                                   f"{inputs.device}")
+    row = ctypes.c_uint64(0)
+    rc = _lib.lib.sv_bn254_fr_lookup_permute_device(inputs.data_ptr(), tables.data_ptr(), inputs.shape[0], form,
+                                                    out[0].data_ptr(), out[1].data_ptr(), ctypes.byref(row), d,
+                                                    _stream_handle(inputs.device))
+    try:
+        _lib.check(rc, "sv_bn254_fr_lookup_permute_device")
+    except _lib.ArgumentError as e:
+        if "not in table" in str(e):
+            e.row = row.value
+        raise
+    return out[0], out[1]
+
+
 def last_msm_stats() -> dict:
     s = _lib.sv_msm_stats()
     _lib.check(_lib.lib.sv_msm_last_stats(ctypes.byref(s)), "sv_msm_last_stats")

@@ -219,6 +219,15 @@ extern "C" {
     /// d_out[i] = 1 / d_in[i], 0 where d_in[i] is 0; d_out == d_in is in place.
     pub fn sv_bn254_fr_batch_invert_device(d_in: *const SvFe, d_out: *mut SvFe, n: usize, form: c_int,
                                            device: c_int, stream: *mut c_void) -> c_int;
+    /// Stable ascending sort of a column in HBM by canonical value; d_out == d_in is in place.
+    pub fn sv_bn254_fr_sort_device(d_in: *const SvFe, d_out: *mut SvFe, n: usize, form: c_int,
+                                   device: c_int, stream: *mut c_void) -> c_int;
+    /// halo2's permute_expression_pair on columns in HBM: A' and S' of a lookup; out_missing_row is a host
+    /// pointer (may be null): the smallest row of A' whose value is not in the table, u64::MAX on success.
+    pub fn sv_bn254_fr_lookup_permute_device(d_input: *const SvFe, d_table: *const SvFe, n: usize, form: c_int,
+                                             d_permuted_input: *mut SvFe, d_permuted_table: *mut SvFe,
+                                             out_missing_row: *mut u64, device: c_int,
+                                             stream: *mut c_void) -> c_int;
     pub fn sv_bn254_shplonk_work_elems(n_sets: usize, n: usize, elems: *mut u64) -> c_int;
     pub fn sv_bn254_shplonk_quotient_device(handle: u64, offset: usize, d_polys: *const *const SvFe,
                                             lens: *const u64, m: usize, sets: *const SvShplonkSet, n_sets: usize,
