@@ -426,6 +426,57 @@ int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size
                            int direction, const sv_fe* shift, int form, int device,
                            void* stream) SV_NOEXCEPT;
 
+/* ---- extended-domain quotient: coset LDE and division by X^n - 1 ---------------------------
+ * The two fixed-function ends of a halo2 prover's quotient, for data that is already in HBM:
+ * EvaluationDomain::coeff_to_extended going in, and divide_by_vanishing_poly, extended_to_coeff and
+ * the h_pieces of vanishing::Argument::construct coming out.  The gate arithmetic between the two
+ * is the caller's.  Throughout n = 2^log_n, K = log_n + log_ext, omega_K = root_of_unity(K),
+ * omega_e = omega_K^n = root_of_unity(log_ext), g = *shift (a host pointer, in `form`).  The library
+ * holds no zeta, as it holds no delta: a halo2 caller passes g = Fr::ZETA = 7^((r - 1) / 3).
+ * fr_coset_lde_device: `count` polynomials of exactly n coefficients each lie back to back in
+ *   d_coeffs (count n elements); polynomial t is extended to 2^K evaluations,
+ *     d_evals[t 2^K + j] = sum_{i<n} d_coeffs[t n + i] (g omega_K^j)^i,   j < 2^K, natural order.
+ *   A NULL shift means 1.  log_ext == 0 is legal and equals the forward coset NTT.  The input is
+ *   only read, and nothing beyond count n elements of it is ever read: no zero-padded copy exists at
+ *   any point, an input index >= n is a zero that is never loaded.  The two ranges must not overlap
+ *   at all ("overlaps", SV_ERR_ARG): there is no in place.
+ *   Checked before any device work, in this order: bad form, a null d_coeffs or d_evals, a pointer
+ *   not 16-byte aligned SV_ERR_ARG; count == 0 SV_ERR_EMPTY; log_ext > SV_EXT_LOG_MAX, K >
+ *   SV_NTT_MAX_LOG or count 2^K > 2^28 SV_ERR_LEN; a shift not below r SV_ERR_ARG ("not reduced"); a
+ *   shift equal to zero SV_ERR_ARG; the overlap SV_ERR_ARG.
+ * fr_quotient_coeffs_device: d_numer holds N(g omega_K^j) for j < 2^K.  With t(X) = X^n - 1,
+ *   q_j = N_j / t(g omega_K^j) and h the unique polynomial of degree < 2^K with h(g omega_K^j) = q_j,
+ *     d_out[i] = h_i   for i < pieces n:
+ *   `pieces` blocks of n coefficients, ready for sv_bn254_g1_msm_bases_device.  The higher
+ *   coefficients are dropped as halo2's truncate drops them, whether or not they are zero, and
+ *   nothing outside [0, pieces n) of d_out is written.  t takes only 2^log_ext values on the coset,
+ *   t(g omega_K^j) = g^n omega_e^(j mod 2^log_ext) - 1: the host builds and inverts them (one field
+ *   inversion) and the first pass reads a table of at most 256 elements.  d_out == d_numer is in
+ *   place; any other overlap of the two ranges is "overlaps".
+ *   Checked before any device work, in this order: bad form, a null d_numer, d_out or shift (a coset
+ *   is required here), a pointer not 16-byte aligned SV_ERR_ARG; pieces == 0 SV_ERR_EMPTY; log_ext >
+ *   SV_EXT_LOG_MAX or K > SV_NTT_MAX_LOG, then pieces > 2^log_ext SV_ERR_LEN; a shift not below r
+ *   SV_ERR_ARG ("not reduced"); a shift equal to zero SV_ERR_ARG; g^(2^K) == 1 SV_ERR_ARG ("coset
+ *   meets the domain": t vanishes somewhere on it; K squarings on the host); the overlap SV_ERR_ARG.
+ * Both: an element not below r is SV_ERR_ARG ("not reduced") for that call, found on the device in
+ * the first pass: the output is then unspecified, nothing outside it is written, and the next call
+ * is exact.  Points 1 and 2 of "Streams" apply (ordered after `stream`, synchronous); re-entrant
+ * from any number of threads.  SVGPU_NTT_TILE_LOG is honoured exactly as by the NTT.  `form` covers
+ * the data and the shift.  All mod r: every output is determined bit for bit.
+ * Scratch (pooled): the NTT's at K -- 256 B, the first pass's flags and, with two or more passes
+ * (K > 10), one image of count 2^K elements -- plus, for the quotient, the table (2^log_ext x 32 B)
+ * and as many bytes of pinned host memory for its one small copy on the call's stream.
+ * Not covered: the numerator itself (gate, permutation and lookup expressions); blinding of h; host
+ * buffers; multi-device columns; several quotients per call; a check that the dropped high
+ * coefficients are zero.                                                                      */
+#define SV_EXT_LOG_MAX 8
+int sv_bn254_fr_coset_lde_device(const sv_fe* d_coeffs, sv_fe* d_evals, uint32_t log_n,
+                                 uint32_t log_ext, size_t count, const sv_fe* shift, int form,
+                                 int device, void* stream) SV_NOEXCEPT;
+int sv_bn254_fr_quotient_coeffs_device(const sv_fe* d_numer, sv_fe* d_out, uint32_t log_n,
+                                       uint32_t log_ext, size_t pieces, const sv_fe* shift,
+                                       int form, int device, void* stream) SV_NOEXCEPT;
+
 /* ---- running products and batch inversion over Fr columns in HBM -----------------------
  * The running-product columns of a halo2 prover: the permutation argument's z (one per chunk of
  * columns) and each lookup's z, which satisfy the relations the verifier checks in

@@ -1986,6 +1986,150 @@ int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size
   SV_GUARD_END
 }
 
+// ---- extended-domain quotient: coset LDE and division by X^n - 1 (csrc/ntt.hip, csrc/ext_plan.hpp) ----
+namespace {
+// rule 4 of both calls: a shift below r, then not zero
+int ext_shift_rules(const sv_fe& shift) {
+  if (!host::f_is_reduced(fe_in(shift), host::R64)) {
+    sv::set_error("shift not reduced mod the scalar field order");
+    return SV_ERR_ARG;
+  }
+  if ((shift.l[0] | shift.l[1] | shift.l[2] | shift.l[3]) == 0) {
+    sv::set_error("shift is zero: the coset has no inverse");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+
+// both calls past their checks: the error flag after the stream has drained
+int ext_finish(DrainedLease* dl) {
+  Workspace* ws = dl->ws();
+  SV_HIP(hipMemcpyAsync(ws->pinned, ws->buf + kNttErrOffset, sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl->armed = false;
+  uint32_t errv;
+  memcpy(&errv, ws->pinned, sizeof errv);
+  if (errv) {
+    sv::set_error("invalid input: element not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+}  // namespace
+
+int sv_bn254_fr_coset_lde_device(const sv_fe* d_coeffs, sv_fe* d_evals, uint32_t log_n, uint32_t log_ext,
+                                 size_t count, const sv_fe* shift, int form, int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_coeffs || !d_evals) {
+    sv::set_error("null pointer");
+    return SV_ERR_ARG;
+  }
+  if (((uintptr_t)d_coeffs | (uintptr_t)d_evals) & 15u) {
+    sv::set_error("d_coeffs and d_evals must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (count == 0) {
+    sv::set_error("the batch should not be empty");
+    return SV_ERR_EMPTY;
+  }
+  if (log_ext > SV_EXT_LOG_MAX || log_n > SV_NTT_MAX_LOG || log_n + log_ext > SV_NTT_MAX_LOG ||
+      count > ((size_t(1) << 28) >> (log_n + log_ext))) {
+    sv::set_error("log_n = %u, log_ext = %u, count = %zu: beyond log_ext %d, 2^%d points per transform or 2^28 "
+                  "elements per call", log_n, log_ext, count, SV_EXT_LOG_MAX, SV_NTT_MAX_LOG);
+    return SV_ERR_LEN;
+  }
+  LdeCall call{};
+  call.has_shift = false;
+  if (shift) {
+    SV_TRY(ext_shift_rules(*shift));
+    sv_fe one = {{1, 0, 0, 0}};
+    if (form == SV_MONTGOMERY) one = poly_fr_one();
+    call.has_shift = memcmp(shift->l, one.l, sizeof one.l) != 0;
+    call.shift = *shift;
+  }
+  const size_t in_bytes = (count << log_n) * sizeof(sv_fe), out_bytes = (count << (log_n + log_ext)) * sizeof(sv_fe);
+  const uintptr_t ib = (uintptr_t)d_coeffs, ob = (uintptr_t)d_evals;
+  if (ib < ob + out_bytes && ob < ib + in_bytes) {
+    sv::set_error("d_evals overlaps d_coeffs (the extension is never in place)");
+    return SV_ERR_ARG;
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  call.d_coeffs = d_coeffs;
+  call.d_evals = d_evals;
+  call.log_n = log_n;
+  call.log_ext = log_ext;
+  call.count = count;
+  call.form = form;
+  call.tile_log = ntt_tile_log();
+  SV_TRY(ws->reserve(lde_scratch_bytes(log_n, log_ext, count, call.tile_log)));
+  SV_TRY(ws->reserve_pinned(kNttHeadBytes));
+  SV_TRY(lde_enqueue(call, device, ws->buf, ws->stream));
+  return ext_finish(&dl);
+  SV_GUARD_END
+}
+
+int sv_bn254_fr_quotient_coeffs_device(const sv_fe* d_numer, sv_fe* d_out, uint32_t log_n, uint32_t log_ext,
+                                       size_t pieces, const sv_fe* shift, int form, int device,
+                                       void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!d_numer || !d_out || !shift) {
+    sv::set_error("null pointer (the quotient needs a coset: shift may not be NULL)");
+    return SV_ERR_ARG;
+  }
+  if (((uintptr_t)d_numer | (uintptr_t)d_out) & 15u) {
+    sv::set_error("d_numer and d_out must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (pieces == 0) {
+    sv::set_error("the quotient should not be empty (pieces == 0)");
+    return SV_ERR_EMPTY;
+  }
+  if (log_ext > SV_EXT_LOG_MAX || log_n > SV_NTT_MAX_LOG || log_n + log_ext > SV_NTT_MAX_LOG) {
+    sv::set_error("log_n = %u, log_ext = %u: beyond log_ext %d or 2^%d points per transform", log_n, log_ext,
+                  SV_EXT_LOG_MAX, SV_NTT_MAX_LOG);
+    return SV_ERR_LEN;
+  }
+  if (pieces > (size_t(1) << log_ext)) {
+    sv::set_error("pieces = %zu: the extended domain holds 2^%u pieces of 2^%u coefficients", pieces, log_ext, log_n);
+    return SV_ERR_LEN;
+  }
+  SV_TRY(ext_shift_rules(*shift));
+  const uint32_t K = log_n + log_ext;
+  if (coset_meets_domain(*shift, form, K)) {
+    sv::set_error("coset meets the domain: shift^(2^%u) == 1, so X^n - 1 vanishes on it", K);
+    return SV_ERR_ARG;
+  }
+  const size_t in_bytes = (size_t(1) << K) * sizeof(sv_fe), out_bytes = (pieces << log_n) * sizeof(sv_fe);
+  const uintptr_t ib = (uintptr_t)d_numer, ob = (uintptr_t)d_out;
+  if (ib != ob && ib < ob + out_bytes && ob < ib + in_bytes) {
+    sv::set_error("d_out overlaps d_numer without being d_numer (in place is d_out == d_numer)");
+    return SV_ERR_ARG;
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  QuotCall call{};
+  call.d_numer = d_numer;
+  call.d_out = d_out;
+  call.log_n = log_n;
+  call.log_ext = log_ext;
+  call.pieces = pieces;
+  call.shift = *shift;
+  call.form = form;
+  call.tile_log = ntt_tile_log();
+  SV_TRY(ws->reserve(quotient_scratch_bytes(log_n, log_ext, call.tile_log)));
+  SV_TRY(ws->reserve_pinned(kNttHeadBytes + quotient_stage_bytes(log_ext)));
+  SV_TRY(quotient_enqueue(call, device, ws->buf, ws->pinned + kNttHeadBytes, ws->stream));
+  return ext_finish(&dl);
+  SV_GUARD_END
+}
+
 // ---- running products and batch inversion over Fr columns (csrc/grand_product.hip) ----
 namespace {
 bool fr_reduced(const sv_fe& a) { return host::f_is_reduced(fe_in(a), host::R64); }

@@ -33,6 +33,19 @@
 //
 // An element not below r is found in the first pass; a block's flag is a plain store and one small
 // launch folds the flags: nothing is zeroed per call.
+//
+// The extended-domain round trip (ext_plan.hpp has its predicates) runs the same passes.  k_ntt_pass
+// is a template over the mode; kNtt is the transform above and compiles to what it was.
+//   kLde   pass 0 of a coset LDE: n = 2^k coefficients into the plan of K = k + e.  An input index
+//          >= n is a zero that is never loaded (no padded copy exists in HBM), the way-in factor
+//          goes to live elements only, a block whose columns are all padding stores zeros and
+//          leaves, and in the first min(e, w_0) stages the upper partner of a butterfly is a known
+//          zero: sum = p stays where it is, difference = p omega^j, and a pair whose lower partner
+//          is padding too is skipped.  Passes 1 .. are kNtt.
+//   kQuot  the first and the last pass of the quotient's inverse coset transform: the way-in factor
+//          is table[i mod 2^e] = c / t(g omega_K^i) (c the conversion constant, folded in on the
+//          host; at most 256 entries at the head of the call's scratch), and the digit-reversed
+//          store of the last pass skips every destination index >= pieces n.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -41,6 +54,7 @@
 #include <vector>
 
 #include "field.hpp"
+#include "ext_plan.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
 
@@ -59,7 +73,8 @@ constexpr uint32_t kTabLog = 13;                  // entries per table (log2)
 constexpr uint32_t kTabMask = (1u << kTabLog) - 1u;
 static_assert(kNttMaxLog <= kRootLog && kRootLog == 2 * kTabLog, "omega_26^e = hi[e >> 13] lo[e & 8191]");
 
-enum : int { kNone = 0, kConst = 1, kPowers = 2 };  // the per-element factor of a side
+enum : int { kNone = 0, kConst = 1, kPowers = 2, kTable = 3 };  // the per-element factor of a side
+enum : int { kNtt = 0, kLde = 1, kQuot = 2 };                        // k_ntt_pass's modes
 
 struct PassArgs {
   const uint4* src;
@@ -73,6 +88,11 @@ struct PassArgs {
   int in_mode, out_mode;
   Fr in_c, out_c;        // the constant of either side
   Fr pw[kNttMaxLog];     // g^(2^b) (forward) or g^-(2^b) (inverse), Montgomery
+  // kLde, kQuot only
+  uint32_t live_log;     // kLde: input indices below 2^live_log are coefficients, the rest zeros
+  uint32_t ext_log;      // e
+  uint64_t keep;         // kQuot: destination indices below it are stored
+  const Fr* table;       // kQuot: c / t_i, 2^e entries
 };
 
 __device__ __forceinline__ Fr ld_el(const uint4* sm, uint32_t x) {
@@ -95,6 +115,7 @@ __device__ __forceinline__ Fr pow_seeds(const Fr& c, const Fr (&pw)[kNttMaxLog],
   return r;
 }
 
+template <int kMode>
 __global__ void __launch_bounds__(kNT) k_ntt_pass(const PassArgs a) {
   __shared__ uint4 sm[kPlane + kElems];
   const uint32_t t = threadIdx.x;
@@ -114,19 +135,40 @@ __global__ void __launch_bounds__(kNT) k_ntt_pass(const PassArgs a) {
   const bool live_u = gu < a.total_cols;
   const uint32_t col_u = (uint32_t)(gu & ((1ull << cl) - 1ull));
   const uint64_t first_u = (gu >> cl) << k;  // its transform's first element
+  // kLde reads polynomial gu >> cl of 2^live_log coefficients
+  const uint64_t src_first_u = kMode == kLde ? (gu >> cl) << a.live_log : first_u;
   const uint32_t mu0 = t >> (c + 1), mu_step = kNT >> (c + 1);
   // ... and of its whole elements (arithmetic)
   const uint32_t qe = t & cmask;
   const uint32_t col_e = (uint32_t)((g0 + qe) & ((1ull << cl) - 1ull));
   const uint32_t m0 = t >> c, m_step = kNT >> c;
 
+  if (kMode == kLde) {
+    // a block of padding: zeros in the image, a clean flag
+    if (__syncthreads_and(ext_col_dead(a.plan, col_e, a.live_log))) {
+      if (live_u) {
+        const uint64_t base = first_u + ntt_dst_base(a.plan, s, col_u);
+#pragma unroll
+        for (uint32_t r = 0; r < 2 * kPer; r++) {
+          const uint32_t m = mu0 + r * mu_step;
+          if (t + r * kNT < 2 * elems) a.dst[2 * (base + ((uint64_t)m << dl)) + half] = make_uint4(0, 0, 0, 0);
+        }
+      }
+      if (t == 0) a.flags[blockIdx.x] = 0u;
+      return;
+    }
+  }
+
   {
-    const uint64_t base = first_u + ntt_src_base(a.plan, s, col_u);
+    const uint32_t sb = ntt_src_base(a.plan, s, col_u);
+    const uint64_t base = src_first_u + sb;
     uint4 v[2 * kPer];
 #pragma unroll
     for (uint32_t r = 0; r < 2 * kPer; r++) {
       const uint32_t m = mu0 + r * mu_step;
-      v[r] = live_u && t + r * kNT < 2 * elems ? a.src[2 * (base + ((uint64_t)m << sl)) + half] : make_uint4(0, 0, 0, 0);
+      bool ld = live_u && t + r * kNT < 2 * elems;
+      if (kMode == kLde) ld = ld && ext_live(sb + (m << sl), a.live_log);
+      v[r] = ld ? a.src[2 * (base + ((uint64_t)m << sl)) + half] : make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
     for (uint32_t r = 0; r < 2 * kPer; r++) {
@@ -140,16 +182,21 @@ __global__ void __launch_bounds__(kNT) k_ntt_pass(const PassArgs a) {
   if (a.flags != nullptr) {
     bool bad = false;
     Fr f = a.in_c;
-    if (a.in_mode == kPowers) f = pow_seeds(a.in_c, a.pw, ntt_src_base(a.plan, s, col_e) + (m0 << sl), k);
+    const uint32_t i0 = ntt_src_base(a.plan, s, col_e) + (m0 << sl);
+    // kLde: a thread's live elements are a prefix of its elements (the index grows with r)
+    if (a.in_mode == kPowers && (kMode != kLde || ext_live(i0, a.live_log))) f = pow_seeds(a.in_c, a.pw, i0, k);
+    const bool per_element = kMode == kQuot && !ext_table_shared(a.plan, a.ext_log);
+    if (kMode == kQuot && a.in_mode == kTable) f = a.table[ext_table_index(a.plan, col_e, m0, a.ext_log)];
     const uint32_t step = sl + kTL - c;  // g^(m_step 2^sl): at most k - 2 (the index below is clamped all the same)
     const Fr fstep = a.pw[step < kNttMaxLog ? step : kNttMaxLog - 1];
 #pragma unroll 1
     for (uint32_t r = 0; r < kPer; r++) {
       const uint32_t x = t + r * kNT;
-      if (x < elems) {
+      if (x < elems && (kMode != kLde || ext_live(i0 + ((r * m_step) << sl), a.live_log))) {
         Fr v = ld_el(sm, x);
         bad |= !v.is_reduced();
         if (a.in_mode != kNone) {
+          if (per_element && r > 0) f = a.table[ext_table_index(a.plan, col_e, m0 + r * m_step, a.ext_log)];
           st_el(sm, x, v * f);
           if (a.in_mode == kPowers) f = f * fstep;
         }
@@ -160,6 +207,7 @@ __global__ void __launch_bounds__(kNT) k_ntt_pass(const PassArgs a) {
   }
 
   // the w stages, kPer / 2 butterflies per thread between barriers
+  const uint32_t zero_stages = kMode == kLde ? ext_zero_stages(a.plan, a.ext_log) : 0u;
   for (int st = (int)w - 1; st >= 0; st--) {
     Fr lo_v[kPer / 2], hi_v[kPer / 2];
 #pragma unroll
@@ -169,6 +217,13 @@ __global__ void __launch_bounds__(kNT) k_ntt_pass(const PassArgs a) {
         uint32_t m, j;
         ntt_stage_pair(b >> c, (uint32_t)st, &m, &j);
         const uint32_t x0 = (m << c) | (b & cmask), x1 = x0 + (1u << (st + c));
+        if (kMode == kLde && (uint32_t)st + zero_stages >= w) {  // q = 0: the sum is p, in place
+          if (ext_pair_dead(a.plan, a.ext_log, (uint32_t)st, m)) continue;  // p = 0 too: x1 stays zero
+          hi_v[r] = ld_el(sm, x0);
+          if (st > 0) hi_v[r] = hi_v[r] * a.tab_hi[ntt_stage_exp(j, (uint32_t)st, kRootLog) >> kTabLog];
+          st_el(sm, x1, hi_v[r]);
+          continue;
+        }
         const Fr p = ld_el(sm, x0), q = ld_el(sm, x1);
         lo_v[r] = p + q;
         hi_v[r] = p - q;
@@ -216,11 +271,14 @@ __global__ void __launch_bounds__(kNT) k_ntt_pass(const PassArgs a) {
   }
 
   if (live_u) {
-    const uint64_t base = first_u + ntt_dst_base(a.plan, s, col_u);
+    const uint32_t db = ntt_dst_base(a.plan, s, col_u);
+    const uint64_t base = first_u + db;
+    const bool cut = kMode == kQuot && ntt_is_last(a.plan, s);
 #pragma unroll
     for (uint32_t r = 0; r < 2 * kPer; r++) {
       const uint32_t m = mu0 + r * mu_step;
-      if (t + r * kNT < 2 * elems) a.dst[2 * (base + ((uint64_t)m << dl)) + half] = sm[half * kPlane + ((m << c) | qu)];
+      if (t + r * kNT < 2 * elems && (!cut || ext_kept(db + (m << dl), a.keep)))
+        a.dst[2 * (base + ((uint64_t)m << dl)) + half] = sm[half * kPlane + ((m << c) | qu)];
     }
   }
 }
@@ -379,9 +437,155 @@ int ntt_enqueue(const NttCall& call, int device, void* d_scratch, hipStream_t st
     a.in_c = in_c;
     a.out_mode = last ? out_mode : kNone;
     a.out_c = out_c;
-    hipLaunchKernelGGL(k_ntt_pass, dim3(pass_blocks(plan, s, call.count)), dim3(kNT), 0, st, a);
+    hipLaunchKernelGGL(k_ntt_pass<kNtt>, dim3(pass_blocks(plan, s, call.count)), dim3(kNT), 0, st, a);
   }
   hipLaunchKernelGGL(k_ntt_flags, dim3(1), dim3(kNT), 0, st, flags, pass_blocks(plan, 0, call.count), err);
+  SV_HIP(hipGetLastError());
+  return SV_OK;
+}
+
+// ---- the extended-domain round trip: coset LDE in, quotient coefficients out ----
+namespace {
+
+// what both calls share with ntt_enqueue: the tables of a direction, the plan, the seeds of g
+int ext_args(PassArgs* a, uint32_t K, uint32_t tile_log, bool inverse, Fr g, int device, hipStream_t st) {
+  const Fr* tabs;
+  SV_TRY(tables_for(device, st, &tabs));
+  const size_t tn = size_t(1) << kTabLog;
+  memset(a, 0, sizeof *a);
+  a->tab_hi = tabs + (inverse ? 2 * tn : 0);
+  a->tab_lo = a->tab_hi + tn;
+  a->plan = ntt_make_plan(K, tile_log);
+  for (uint32_t b = 0; b < kNttMaxLog; b++) {
+    a->pw[b] = g;
+    g = fe_sqr(g);
+  }
+  return SV_OK;
+}
+
+size_t ext_table_bytes(uint32_t log_ext) { return ((sizeof(Fr) << log_ext) + 255) & ~size_t(255); }
+
+}  // namespace
+
+size_t lde_scratch_bytes(uint32_t log_n, uint32_t log_ext, size_t count, uint32_t tile_log) {
+  return ntt_scratch_bytes(log_n + log_ext, count, tile_log);
+}
+
+int lde_enqueue(const LdeCall& call, int device, void* d_scratch, hipStream_t st) {
+  const uint32_t K = call.log_n + call.log_ext;
+  const bool mont = call.form == SV_MONTGOMERY;
+  Fr g = Fr::one();
+  if (call.has_shift) {
+    g = fr_in(call.shift);
+    if (!mont) g = fe_to_mont(g);
+  }
+  PassArgs a;
+  SV_TRY(ext_args(&a, K, call.tile_log, false, g, device, st));
+  const NttPlan& plan = a.plan;
+  const uint32_t launches = ntt_launches(plan);
+
+  char* scratch = static_cast<char*>(d_scratch);
+  uint32_t* err = reinterpret_cast<uint32_t*>(scratch + kNttErrOffset);
+  uint32_t* flags = reinterpret_cast<uint32_t*>(scratch + kNttHeadBytes);
+  uint4* image = reinterpret_cast<uint4*>(scratch + kNttHeadBytes + flags_bytes(plan, call.count));
+
+  Fr raw_one = Fr::zero();
+  raw_one.v[0] = 1;
+  a.in_c = mont ? Fr::one() : fe_to_mont(Fr::one());  // R, or R^2
+  a.out_c = mont ? Fr::one() : raw_one;
+  a.live_log = call.log_n;
+  a.ext_log = call.log_ext;
+  for (uint32_t s = 0; s < launches; s++) {
+    const bool first = s == 0, last = s + 1 == launches;
+    a.src = first ? static_cast<const uint4*>(call.d_coeffs) : image;
+    a.dst = last ? static_cast<uint4*>(call.d_evals) : image;
+    a.flags = first ? flags : nullptr;
+    a.total_cols = (uint64_t)call.count << ntt_cols_log(plan, s);
+    a.pass = s;
+    a.in_mode = !first ? kNone : call.has_shift ? kPowers : mont ? kNone : kConst;
+    a.out_mode = last && !mont ? kConst : kNone;
+    const dim3 grid(pass_blocks(plan, s, call.count));
+    if (first) hipLaunchKernelGGL(k_ntt_pass<kLde>, grid, dim3(kNT), 0, st, a);
+    else hipLaunchKernelGGL(k_ntt_pass<kNtt>, grid, dim3(kNT), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_ntt_flags, dim3(1), dim3(kNT), 0, st, flags, pass_blocks(plan, 0, call.count), err);
+  SV_HIP(hipGetLastError());
+  return SV_OK;
+}
+
+size_t quotient_scratch_bytes(uint32_t log_n, uint32_t log_ext, uint32_t tile_log) {
+  return ext_table_bytes(log_ext) + ntt_scratch_bytes(log_n + log_ext, 1, tile_log);
+}
+size_t quotient_stage_bytes(uint32_t log_ext) { return ext_table_bytes(log_ext); }
+
+bool coset_meets_domain(const sv_fe& shift, int form, uint32_t log_size) {
+  Fr g = fr_in(shift);
+  if (form != SV_MONTGOMERY) g = fe_to_mont(g);
+  for (uint32_t i = 0; i < log_size; i++) g = fe_sqr(g);
+  return memcmp(g.v, Fr::one().v, sizeof g.v) == 0;
+}
+
+int quotient_enqueue(const QuotCall& call, int device, void* d_scratch, void* h_stage, hipStream_t st) {
+  const uint32_t k = call.log_n, e = call.log_ext, K = k + e;
+  const bool mont = call.form == SV_MONTGOMERY;
+  Fr g = fr_in(call.shift);
+  if (!mont) g = fe_to_mont(g);
+  PassArgs a;
+  SV_TRY(ext_args(&a, K, call.tile_log, true, fe_inv(g), device, st));
+  const NttPlan& plan = a.plan;
+  const uint32_t launches = ntt_launches(plan);
+
+  // table[i] = c / (g^n omega_e^i - 1), i < 2^e: one inversion (no t_i is zero: g^(2^K) != 1)
+  const size_t m = size_t(1) << e;
+  Fr gn = g;
+  for (uint32_t i = 0; i < k; i++) gn = fe_sqr(gn);
+  const Fr we = root_mont(e);
+  std::vector<Fr> t(m), pre(m);
+  Fr x = gn, acc = Fr::one();
+  for (size_t i = 0; i < m; i++) {
+    t[i] = x - Fr::one();
+    pre[i] = acc;
+    acc = acc * t[i];
+    x = x * we;
+  }
+  Fr inv = fe_inv(acc);
+  Fr* stage = static_cast<Fr*>(h_stage);
+  for (size_t i = m; i-- > 0;) {
+    const Fr ti = inv * pre[i];
+    inv = inv * t[i];
+    stage[i] = mont ? ti : fe_to_mont(ti);  // canonical data: the table carries the R^2 of the conversion
+  }
+
+  char* scratch = static_cast<char*>(d_scratch);
+  const size_t tb = ext_table_bytes(e);
+  uint32_t* err = reinterpret_cast<uint32_t*>(scratch + kNttErrOffset);
+  Fr* table = reinterpret_cast<Fr*>(scratch + kNttHeadBytes);
+  uint32_t* flags = reinterpret_cast<uint32_t*>(scratch + kNttHeadBytes + tb);
+  uint4* image = reinterpret_cast<uint4*>(scratch + kNttHeadBytes + tb + flags_bytes(plan, 1));
+  SV_HIP(hipMemcpyAsync(table, stage, m * sizeof(Fr), hipMemcpyHostToDevice, st));
+
+  Fr n = Fr::one();
+  for (uint32_t i = 0; i < K; i++) n = n + n;
+  const Fr ninv = fe_inv(n);
+  a.in_c = Fr::one();
+  a.out_c = mont ? ninv : fe_from_mont(ninv);
+  a.ext_log = e;
+  a.keep = (uint64_t)call.pieces << k;
+  a.table = table;
+  for (uint32_t s = 0; s < launches; s++) {
+    const bool first = s == 0, last = s + 1 == launches;
+    a.src = first ? static_cast<const uint4*>(call.d_numer) : image;
+    a.dst = last ? static_cast<uint4*>(call.d_out) : image;
+    a.flags = first ? flags : nullptr;
+    a.total_cols = 1ull << ntt_cols_log(plan, s);
+    a.pass = s;
+    a.in_mode = first ? kTable : kNone;
+    a.out_mode = last ? kPowers : kNone;
+    const dim3 grid(pass_blocks(plan, s, 1));
+    if (first || last) hipLaunchKernelGGL(k_ntt_pass<kQuot>, grid, dim3(kNT), 0, st, a);
+    else hipLaunchKernelGGL(k_ntt_pass<kNtt>, grid, dim3(kNT), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_ntt_flags, dim3(1), dim3(kNT), 0, st, flags, pass_blocks(plan, 0, 1), err);
   SV_HIP(hipGetLastError());
   return SV_OK;
 }

@@ -66,6 +66,40 @@ def ntt_device(data, **kwargs):
     return run(data, **kwargs)
 
 
+def coset_lde_device(coeffs, log_ext, **kwargs):
+    """svgpu.device.coset_lde_device (imported on first use: that module needs torch)."""
+    from .device import coset_lde_device as run
+    return run(coeffs, log_ext, **kwargs)
+
+
+def quotient_coeffs_device(numer, log_n, pieces, shift, **kwargs):
+    """svgpu.device.quotient_coeffs_device (imported on first use: that module needs torch)."""
+    from .device import quotient_coeffs_device as run
+    return run(numer, log_n, pieces, shift, **kwargs)
+
+
+def extended_k(k: int, degree: int) -> int:
+    """halo2's EvaluationDomain rule for the extended domain of a circuit of 2^k rows whose
+    constraints have degree `degree`: the smallest K >= k with 2^K >= 2^k (degree - 1).  The quotient
+    then has degree - 1 pieces of 2^k coefficients."""
+    if k < 0 or degree < 2:
+        raise LengthError(f"extended_k: k = {k}, degree = {degree}: a circuit has k >= 0 and degree >= 2")
+    K = k
+    while (1 << K) < (1 << k) * (degree - 1):
+        K += 1
+    return K
+
+
+def commit_pieces(bases: ResidentBases, h, n: int, form: int = SV_MONTGOMERY):
+    """The commitments of the quotient's pieces: h is the (pieces n, 4) tensor quotient_coeffs_device
+    returns (limbs in `form`, on the set's device), piece i its rows [i n, (i + 1) n); one
+    msm_bases_device per piece over set[0:n] -> a list of affine points (None = identity)."""
+    rows = h.shape[0]
+    if n <= 0 or rows == 0 or rows % n:
+        raise LengthError(f"commit_pieces: {rows} rows are not a positive number of pieces of {n}")
+    return [bases.msm_device(h[i * n:(i + 1) * n], offset=0, form=form) for i in range(rows // n)]
+
+
 def grand_product_device(num, den, **kwargs):
     """svgpu.device.grand_product_device (imported on first use: that module needs torch)."""
     from .device import grand_product_device as run

@@ -24,6 +24,7 @@ SV_EVAL_POINTS_MAX = 16   # points per evaluation call, roots per division, poin
 SV_NTT_MAX_LOG = 26        # log2 of the longest transform
 SV_NTT_FORWARD = 0
 SV_NTT_INVERSE = 1
+SV_EXT_LOG_MAX = 8         # log2 of the widest extension of coset_lde / quotient_coeffs
 
 SV_FACTOR_PLAIN = 0        # f[i] = x[i] + c
 SV_FACTOR_COLUMN = 1       # f[i] = x[i] + s*y[i] + c
@@ -163,6 +164,10 @@ PROTOTYPES = [
     ("sv_bn254_fr_root_of_unity", c_int, [c_uint32, c_int, POINTER(sv_fe)]),
     ("sv_bn254_fr_ntt_device", c_int, [c_void_p, c_void_p, c_uint32, c_size_t, c_int, c_void_p, c_int, c_int,
                                         c_void_p]),
+    ("sv_bn254_fr_coset_lde_device", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_size_t, c_void_p, c_int,
+                                              c_int, c_void_p]),
+    ("sv_bn254_fr_quotient_coeffs_device", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_size_t, c_void_p,
+                                                    c_int, c_int, c_void_p]),
     ("sv_bn254_fr_grand_product_device", c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, POINTER(sv_fe),
                                                   POINTER(sv_fe), c_int, c_void_p, POINTER(sv_fe), c_int, c_void_p]),
     ("sv_bn254_fr_batch_invert_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

@@ -226,6 +226,71 @@ def ntt_device(data: torch.Tensor, inverse: bool = False, shift: Optional[int] =
     return out
 
 
+def coset_lde_device(coeffs: torch.Tensor, log_ext: int, shift: Optional[int] = None,
+                     form: int = _lib.SV_MONTGOMERY, out: torch.Tensor = None) -> torch.Tensor:
+    """Coset low-degree extension of HBM-resident coefficients: an (n, 4) int64 tensor of limbs in
+    `form` is one polynomial, a (count, n, 4) tensor `count` polynomials back to back; n is a power of
+    two (else LengthError).  out[j] = sum_i coeffs[i] (shift omega_K^j)^i for j < 2^log_ext n, with
+    omega_K = root_of_unity(log2 n + log_ext), natural order: (2^log_ext n, 4) or (count, 2^log_ext n,
+    4).  shift: a canonical int, None = 1.  out=None allocates; an `out` must not overlap coeffs."""
+    d = _dev_index(coeffs)
+    if coeffs.dtype != torch.int64 or coeffs.dim() not in (2, 3) or coeffs.shape[-1] != 4 or not coeffs.is_contiguous():
+        raise _lib.ArgumentError("coset_lde: coeffs is a contiguous (n, 4) or (count, n, 4) int64 tensor of limbs")
+    n = coeffs.shape[-2]
+    count = coeffs.shape[0] if coeffs.dim() == 3 else 1
+    if n == 0 or n & (n - 1):
+        raise _lib.LengthError(f"coset_lde: {n} coefficients per polynomial is not a power of two")
+    if not 0 <= log_ext <= _lib.SV_EXT_LOG_MAX:
+        raise _lib.LengthError(f"coset_lde: log_ext = {log_ext} is not in 0 .. {_lib.SV_EXT_LOG_MAX}")
+    shape = tuple(coeffs.shape[:-2]) + (n << log_ext, 4)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int64, device=coeffs.device)
+    elif (out.device != coeffs.device or out.dtype != torch.int64 or not out.is_contiguous()
+          or tuple(out.shape) != shape):
+        raise _lib.LengthError(f"coset_lde: out must be a contiguous {shape} int64 tensor on {coeffs.device}")
+    gs = enc.fr_struct(shift, form) if shift is not None else None
+    _lib.check(_lib.lib.sv_bn254_fr_coset_lde_device(coeffs.data_ptr(), out.data_ptr(), n.bit_length() - 1, log_ext,
+                                                     count, ctypes.byref(gs) if gs is not None else None, form, d,
+                                                     _stream_handle(coeffs.device)),
+               "sv_bn254_fr_coset_lde_device")
+    return out
+
+
+def quotient_coeffs_device(numer: torch.Tensor, log_n: int, pieces: int, shift: int,
+                           form: int = _lib.SV_MONTGOMERY, out: torch.Tensor = None) -> torch.Tensor:
+    """The quotient's coefficients from the numerator's evaluations on the extended coset: numer is a
+    (2^K, 4) int64 tensor of limbs in `form`, numer[j] = N(shift omega_K^j); with n = 2^log_n the
+    result is the first pieces n coefficients of the polynomial that takes N_j / ((shift omega_K^j)^n
+    - 1) there: (pieces n, 4), `pieces` blocks of n.  shift: a canonical int (required).  out=None
+    allocates, out=numer is in place (the first pieces n rows of numer are returned); any other `out`
+    (at least pieces n rows) must not overlap numer, and nothing past its first pieces n rows is
+    written."""
+    d = _dev_index(numer)
+    if numer.dtype != torch.int64 or numer.dim() != 2 or numer.shape[-1] != 4 or not numer.is_contiguous():
+        raise _lib.ArgumentError("quotient_coeffs: numer is a contiguous (2^K, 4) int64 tensor of limbs")
+    N = numer.shape[0]
+    if N == 0 or N & (N - 1):
+        raise _lib.LengthError(f"quotient_coeffs: {N} evaluations is not a power of two")
+    K = N.bit_length() - 1
+    if not 0 <= log_n <= K:
+        raise _lib.LengthError(f"quotient_coeffs: log_n = {log_n} is not in 0 .. {K}")
+    if pieces < 0 or pieces > N >> log_n:
+        raise _lib.LengthError(f"quotient_coeffs: pieces = {pieces}: the extended domain holds {N >> log_n} pieces")
+    keep = pieces << log_n
+    if out is None:
+        out = torch.empty((max(keep, 1), 4), dtype=torch.int64, device=numer.device)
+    elif (out.device != numer.device or out.dtype != torch.int64 or not out.is_contiguous() or out.dim() != 2
+          or out.shape[1] != 4 or out.shape[0] < min(keep, N)):
+        raise _lib.LengthError(f"quotient_coeffs: out must be a contiguous (>= {keep}, 4) int64 tensor on {numer.device}")
+    gs = enc.fr_struct(shift, form) if shift is not None else None
+    _lib.check(_lib.lib.sv_bn254_fr_quotient_coeffs_device(numer.data_ptr(), out.data_ptr(), log_n, K - log_n,
+                                                           pieces,
+                                                           ctypes.byref(gs) if gs is not None else None, form, d,
+                                                           _stream_handle(numer.device)),
+               "sv_bn254_fr_quotient_coeffs_device")
+    return out[:keep]
+
+
 # One factor of a grand product: kind (SV_FACTOR_*), x and -- COLUMN -- y as (n, 4) int64 tensors of
 # limbs, s and c as canonical ints.  A plain tuple of the same fields, shorter where the rest is
 # the default, does as well.

@@ -92,6 +92,8 @@ pub const SV_EVAL_POINTS_MAX: usize = 16;
 pub const SV_NTT_MAX_LOG: u32 = 26;
 pub const SV_NTT_FORWARD: c_int = 0;
 pub const SV_NTT_INVERSE: c_int = 1;
+/// log2 of the widest extension sv_bn254_fr_coset_lde_device / _quotient_coeffs_device take.
+pub const SV_EXT_LOG_MAX: u32 = 8;
 /// sv_fr_factor: one factor of a grand product; `kind` is one of the SV_FACTOR_* values.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -210,6 +212,16 @@ extern "C" {
     pub fn sv_bn254_fr_ntt_device(d_in: *const SvFe, d_out: *mut SvFe, log_n: u32, count: usize,
                                   direction: c_int, shift: *const SvFe, form: c_int, device: c_int,
                                   stream: *mut c_void) -> c_int;
+    /// Coset LDE of `count` polynomials of 2^log_n coefficients in HBM to 2^(log_n + log_ext)
+    /// evaluations each on shift * omega^j; `shift` a host pointer (null = 1); never in place.
+    pub fn sv_bn254_fr_coset_lde_device(d_coeffs: *const SvFe, d_evals: *mut SvFe, log_n: u32, log_ext: u32,
+                                        count: usize, shift: *const SvFe, form: c_int, device: c_int,
+                                        stream: *mut c_void) -> c_int;
+    /// Numerator evaluations on the extended coset -> the first pieces * 2^log_n coefficients of the
+    /// quotient by X^n - 1; `shift` a host pointer (required), d_out == d_numer in place.
+    pub fn sv_bn254_fr_quotient_coeffs_device(d_numer: *const SvFe, d_out: *mut SvFe, log_n: u32, log_ext: u32,
+                                              pieces: usize, shift: *const SvFe, form: c_int, device: c_int,
+                                              stream: *mut c_void) -> c_int;
     /// Running product z[0] = z0, z[i + 1] = z[i] num(i) / den(i) over columns in HBM; descriptor arrays
     /// and z0 / omega / out_total are host pointers (omega, out_total may be null).
     pub fn sv_bn254_fr_grand_product_device(num: *const SvFrFactor, n_num: usize, den: *const SvFrFactor,
