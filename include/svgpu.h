@@ -466,9 +466,9 @@ int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size
  * Scratch (pooled): the NTT's at K -- 256 B, the first pass's flags and, with two or more passes
  * (K > 10), one image of count 2^K elements -- plus, for the quotient, the table (2^log_ext x 32 B)
  * and as many bytes of pinned host memory for its one small copy on the call's stream.
- * Not covered: the numerator itself (gate, permutation and lookup expressions); blinding of h; host
- * buffers; multi-device columns; several quotients per call; a check that the dropped high
- * coefficients are zero.                                                                      */
+ * Not covered: custom gate expressions of the numerator (its permutation and lookup terms: the
+ * next block); blinding of h; host buffers; multi-device columns; several quotients per
+ * call; a check that the dropped high coefficients are zero.                                   */
 #define SV_EXT_LOG_MAX 8
 int sv_bn254_fr_coset_lde_device(const sv_fe* d_coeffs, sv_fe* d_evals, uint32_t log_n,
                                  uint32_t log_ext, size_t count, const sv_fe* shift, int form,
@@ -476,6 +476,83 @@ int sv_bn254_fr_coset_lde_device(const sv_fe* d_coeffs, sv_fe* d_evals, uint32_t
 int sv_bn254_fr_quotient_coeffs_device(const sv_fe* d_numer, sv_fe* d_out, uint32_t log_n,
                                        uint32_t log_ext, size_t pieces, const sv_fe* shift,
                                        int form, int device, void* stream) SV_NOEXCEPT;
+
+/* ---- permutation and lookup terms of the quotient numerator -----------------------------
+ * The fixed-function part of the numerator that fr_quotient_coeffs_device divides: the permutation
+ * argument's constraints (snark-verifier/src/system/halo2.rs:501-591) and each lookup's five
+ * (:593-655), joined as :657-668 joins them, by a Horner fold in y (halo2's y, the reference's
+ * alpha).  Notation as in the block above: n = 2^log_n, K = log_n + log_ext, N = 2^K, E =
+ * 2^log_ext, omega_K = root_of_unity(K), g = *shift; row j of an extended column is its value at
+ * X_j = g omega_K^j, natural order, as fr_coset_lde_device leaves it.  A rotation by r rows of the
+ * original domain is rot(c, r)[j] = c[(j + r E) mod N], r of either sign.  Every column is N
+ * elements in HBM on `device`; pointer arrays and scalars are host memory; `form` covers the
+ * columns and every scalar.
+ * Both calls continue one fold: acc starts as d_acc_in[j] (0 when d_acc_in is NULL), every
+ * constraint c in the order listed does acc <- acc y + c[j], and d_out[j] = acc.  The gate
+ * constraints come first in the reference, so a caller folds them into d_acc_in itself; a circuit
+ * with more columns or lookups than a call takes calls again on the running accumulator.  d_out ==
+ * d_acc_in is in place; any other overlap of d_out with an input column is "overlaps".  Only the zk
+ * form of the reference (zk == true) is built.
+ * fr_permutation_terms_device: d_cols[j] and d_sigmas[j], j < m, are the permutation columns v_j and
+ *   sigma_j; s[j] is beta delta^j, passed ready-made (the library holds no delta, as with
+ *   SV_FACTOR_IDENTITY); d_z[i], i < n_z = ceil(m / chunk), the running products.  last_rotation is
+ *   the reference's rotation_last, -(blinding + 1), and must satisfy -n < last_rotation < 0.  A NULL
+ *   shift means 1: the call does not divide, so the plain domain is legal.  Constraints, in order:
+ *     1. l0 (1 - z_0)
+ *     2. l_last (z_last^2 - z_last),                                      z_last = z_(n_z - 1)
+ *     3. l0 (z_i - rot(z_(i-1), last_rotation)),                          i = 1 .. n_z - 1
+ *     4. l_active (rot(z_i, 1) prod_j (v_j + beta sigma_j + gamma) - z_i prod_j (v_j + s_j X + gamma)),
+ *        i = 0 .. n_z - 1, j over chunk i (the last chunk may be short)
+ * fr_lookup_terms_device: per descriptor, in order, with z, a' = d_permuted_input, s' =
+ *   d_permuted_table and the compressed A = d_input, S = d_table on the extended domain (for a
+ *   column-only lookup the LDE of what the lookup's grand product consumed):
+ *     1. l0 (1 - z)
+ *     2. l_last (z^2 - z)
+ *     3. l_active (rot(z, 1) (a' + beta) (s' + gamma) - z (A + beta) (S + gamma))
+ *     4. l0 (a' - s')
+ *     5. l_active (a' - s') (a' - rot(a', -1))
+ * Checked before any device work, in this order (entries beyond a cap are not looked at):
+ *   1. bad form                                                                        SV_ERR_ARG
+ *   2. a null d_out, pointer array, entry of one, l column, s, beta, gamma or y        SV_ERR_ARG
+ *   3. chunk == 0                                                                      SV_ERR_ARG
+ *   4. a column (d_acc_in included) not 16-byte aligned                                SV_ERR_ARG
+ *   5. m == 0 / n_lookups == 0                                                         SV_ERR_EMPTY
+ *   6. log_ext > SV_EXT_LOG_MAX                                                        SV_ERR_LEN
+ *   7. K > SV_NTT_MAX_LOG                                                              SV_ERR_LEN
+ *   8. m > SV_TERMS_COLUMNS_MAX / n_lookups > SV_TERMS_LOOKUPS_MAX                     SV_ERR_LEN
+ *   9. beta, gamma, y, an s[j] or the shift not below r               SV_ERR_ARG ("not reduced")
+ *  10. a shift equal to zero                                                           SV_ERR_ARG
+ *  11. last_rotation outside -n < r < 0                                                SV_ERR_ARG
+ *  12. the overlaps                                                     SV_ERR_ARG ("overlaps")
+ * (the lookup call has no chunk, s, shift or last_rotation: rules 3, 10 and 11 do not arise).  An
+ * element not below r is found on the device and is SV_ERR_ARG ("not reduced") for that call: d_out
+ * is then unspecified, nothing outside it is written, and the next call is exact.  Points 1 and 2
+ * of "Streams" apply (ordered after `stream`, synchronous); re-entrant from any number of threads.
+ * All mod r: every output is determined bit for bit.
+ * Each call is one launch (csrc/quotient_terms.hip) that writes d_out once and holds nothing per
+ * row outside registers.  Pooled scratch: the call's table of column pointers, s_j and powers of y
+ * (under 9 KiB) and as many bytes of pinned host memory for its one small copy on the call's stream.
+ * Not covered: custom gate expressions (they enter through d_acc_in); the non-zk variant; the
+ * theta-compression of several columns into A and S; host buffers; multi-device columns.        */
+#define SV_TERMS_COLUMNS_MAX 64   /* permutation columns per call, and so z columns */
+#define SV_TERMS_LOOKUPS_MAX 16   /* lookups per call */
+typedef struct { const sv_fe* d_z; const sv_fe* d_permuted_input; const sv_fe* d_permuted_table;
+                 const sv_fe* d_input; const sv_fe* d_table; } sv_fr_lookup;
+int sv_bn254_fr_permutation_terms_device(const sv_fe* const* d_cols, const sv_fe* const* d_sigmas,
+                                         const sv_fe* s, size_t m, size_t chunk,
+                                         const sv_fe* const* d_z, const sv_fe* d_l0,
+                                         const sv_fe* d_l_last, const sv_fe* d_l_active,
+                                         const sv_fe* beta, const sv_fe* gamma, const sv_fe* y,
+                                         const sv_fe* shift, int32_t last_rotation,
+                                         const sv_fe* d_acc_in, sv_fe* d_out, uint32_t log_n,
+                                         uint32_t log_ext, int form, int device,
+                                         void* stream) SV_NOEXCEPT;
+int sv_bn254_fr_lookup_terms_device(const sv_fr_lookup* lookups, size_t n_lookups,
+                                    const sv_fe* d_l0, const sv_fe* d_l_last,
+                                    const sv_fe* d_l_active, const sv_fe* beta, const sv_fe* gamma,
+                                    const sv_fe* y, const sv_fe* d_acc_in, sv_fe* d_out,
+                                    uint32_t log_n, uint32_t log_ext, int form, int device,
+                                    void* stream) SV_NOEXCEPT;
 
 /* ---- running products and batch inversion over Fr columns in HBM -----------------------
  * The running-product columns of a halo2 prover: the permutation argument's z (one per chunk of

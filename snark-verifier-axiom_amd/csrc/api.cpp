@@ -28,6 +28,7 @@
 #include "msm_batch_plan.hpp"
 #include "ntt.hpp"
 #include "poseidon.hpp"
+#include "quotient_terms.hpp"
 #include "runtime.hpp"
 
 using namespace sv;
@@ -2295,6 +2296,250 @@ int sv_bn254_fr_batch_invert_device(const sv_fe* d_in, sv_fe* d_out, size_t n, i
   call.invert = true;
   call.d_out = d_out;
   return grand_product_run(call, device, stream, nullptr);
+  SV_GUARD_END
+}
+
+// ---- permutation and lookup terms of the quotient numerator (csrc/quotient_terms.hip) ----
+namespace {
+// What the two calls share: the l columns, the challenges, the accumulator and the output.
+struct TermsCommon {
+  const sv_fe *d_l0, *d_l_last, *d_l_active;
+  const sv_fe *beta, *gamma, *y;
+  const sv_fe* d_acc_in;
+  sv_fe* d_out;
+  uint32_t log_n, log_ext;
+};
+
+// rule 2, the shared part
+int terms_null_rules(const TermsCommon& c) {
+  if (!c.d_out || !c.d_l0 || !c.d_l_last || !c.d_l_active || !c.beta || !c.gamma || !c.y) {
+    sv::set_error("null pointer (d_out, an l column, beta, gamma or y)");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+
+// rule 4, the shared part
+int terms_align_rules(const TermsCommon& c) {
+  if (((uintptr_t)c.d_out | (uintptr_t)c.d_l0 | (uintptr_t)c.d_l_last | (uintptr_t)c.d_l_active |
+       (uintptr_t)c.d_acc_in) & 15u) {
+    sv::set_error("d_out, d_acc_in and the l columns must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+
+// rules 6 to 8
+int terms_size_rules(const TermsCommon& c, size_t count, size_t cap, const char* what) {
+  if (c.log_ext > SV_EXT_LOG_MAX) {
+    sv::set_error("log_ext = %u: beyond log_ext %d", c.log_ext, SV_EXT_LOG_MAX);
+    return SV_ERR_LEN;
+  }
+  if (c.log_n > SV_NTT_MAX_LOG || c.log_n + c.log_ext > SV_NTT_MAX_LOG) {
+    sv::set_error("log_n = %u, log_ext = %u: beyond 2^%d rows per column", c.log_n, c.log_ext, SV_NTT_MAX_LOG);
+    return SV_ERR_LEN;
+  }
+  if (count > cap) {
+    sv::set_error("%zu %s: a call takes at most %zu (call again on the running accumulator)", count, what, cap);
+    return SV_ERR_LEN;
+  }
+  return SV_OK;
+}
+
+// rule 9, the shared part
+int terms_scalar_rules(const TermsCommon& c) {
+  if (!fr_reduced(*c.beta) || !fr_reduced(*c.gamma) || !fr_reduced(*c.y)) {
+    sv::set_error("beta, gamma or y not reduced mod the scalar field order");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+
+// rule 12 for one input column
+int terms_overlap_rule(const TermsCommon& c, const void* column) {
+  const size_t bytes = (size_t(1) << (c.log_n + c.log_ext)) * sizeof(sv_fe);
+  if (ranges_overlap(c.d_out, column, bytes)) {
+    sv::set_error("d_out overlaps an input column (in place is d_out == d_acc_in only)");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+int terms_overlap_rules(const TermsCommon& c) {
+  SV_TRY(terms_overlap_rule(c, c.d_l0));
+  SV_TRY(terms_overlap_rule(c, c.d_l_last));
+  SV_TRY(terms_overlap_rule(c, c.d_l_active));
+  if (c.d_acc_in && c.d_acc_in != c.d_out) SV_TRY(terms_overlap_rule(c, c.d_acc_in));
+  return SV_OK;
+}
+
+// both calls past their checks and their launch: the error flag after the stream has drained
+int terms_finish(DrainedLease* dl, size_t pinned_at) {
+  Workspace* ws = dl->ws();
+  SV_HIP(hipMemcpyAsync(ws->pinned + pinned_at, ws->buf + kQtErrOffset, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                        ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl->armed = false;
+  uint32_t errv;
+  memcpy(&errv, ws->pinned + pinned_at, sizeof errv);
+  if (errv) {
+    sv::set_error("invalid input: element not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+}  // namespace
+
+int sv_bn254_fr_permutation_terms_device(const sv_fe* const* d_cols, const sv_fe* const* d_sigmas, const sv_fe* s,
+                                         size_t m, size_t chunk, const sv_fe* const* d_z, const sv_fe* d_l0,
+                                         const sv_fe* d_l_last, const sv_fe* d_l_active, const sv_fe* beta,
+                                         const sv_fe* gamma, const sv_fe* y, const sv_fe* shift, int32_t last_rotation,
+                                         const sv_fe* d_acc_in, sv_fe* d_out, uint32_t log_n, uint32_t log_ext,
+                                         int form, int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  const TermsCommon c{d_l0, d_l_last, d_l_active, beta, gamma, y, d_acc_in, d_out, log_n, log_ext};
+  SV_TRY(terms_null_rules(c));
+  if (!d_cols || !d_sigmas || !d_z || !s) {
+    sv::set_error("null pointer (d_cols, d_sigmas, d_z or s)");
+    return SV_ERR_ARG;
+  }
+  const size_t seen = std::min(m, (size_t)SV_TERMS_COLUMNS_MAX);  // entries beyond the cap are not looked at
+  const size_t seen_z = chunk ? (seen + chunk - 1) / chunk : 0;
+  uintptr_t bits = 0;
+  for (size_t j = 0; j < seen; j++) {
+    if (!d_cols[j] || !d_sigmas[j]) {
+      sv::set_error("null pointer (permutation column %zu)", j);
+      return SV_ERR_ARG;
+    }
+    bits |= (uintptr_t)d_cols[j] | (uintptr_t)d_sigmas[j];
+  }
+  for (size_t i = 0; i < seen_z; i++) {
+    if (!d_z[i]) {
+      sv::set_error("null pointer (d_z[%zu])", i);
+      return SV_ERR_ARG;
+    }
+    bits |= (uintptr_t)d_z[i];
+  }
+  if (chunk == 0) {
+    sv::set_error("chunk == 0: a z column covers at least one permutation column");
+    return SV_ERR_ARG;
+  }
+  if (bits & 15u) {
+    sv::set_error("the permutation columns, sigmas and z must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  SV_TRY(terms_align_rules(c));
+  if (m == 0) {
+    sv::set_error("the permutation should not be empty (m == 0)");
+    return SV_ERR_EMPTY;
+  }
+  SV_TRY(terms_size_rules(c, m, SV_TERMS_COLUMNS_MAX, "permutation columns"));
+  SV_TRY(terms_scalar_rules(c));
+  for (size_t j = 0; j < m; j++)
+    if (!fr_reduced(s[j])) {
+      sv::set_error("s[%zu] not reduced mod the scalar field order", j);
+      return SV_ERR_ARG;
+    }
+  QtPermCall call{};
+  call.has_shift = false;
+  if (shift) {
+    SV_TRY(ext_shift_rules(*shift));
+    sv_fe one = {{1, 0, 0, 0}};
+    if (form == SV_MONTGOMERY) one = poly_fr_one();
+    call.has_shift = memcmp(shift->l, one.l, sizeof one.l) != 0;
+    call.shift = *shift;
+  }
+  if (last_rotation >= 0 || -(int64_t)last_rotation >= (int64_t(1) << log_n)) {
+    sv::set_error("last_rotation = %d: it must satisfy -2^%u < last_rotation < 0", last_rotation, log_n);
+    return SV_ERR_ARG;
+  }
+  const size_t n_z = (m + chunk - 1) / chunk;
+  SV_TRY(terms_overlap_rules(c));
+  for (size_t j = 0; j < m; j++) {
+    SV_TRY(terms_overlap_rule(c, d_cols[j]));
+    SV_TRY(terms_overlap_rule(c, d_sigmas[j]));
+  }
+  for (size_t i = 0; i < n_z; i++) SV_TRY(terms_overlap_rule(c, d_z[i]));
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  call.d_cols = d_cols, call.d_sigmas = d_sigmas, call.s = s;
+  call.m = m, call.chunk = chunk;
+  call.d_z = d_z;
+  call.d_l0 = d_l0, call.d_l_last = d_l_last, call.d_l_active = d_l_active;
+  call.beta = *beta, call.gamma = *gamma, call.y = *y;
+  call.last_rotation = last_rotation;
+  call.d_acc_in = d_acc_in, call.d_out = d_out;
+  call.log_n = log_n, call.log_ext = log_ext;
+  call.form = form;
+  const size_t tb = Workspace::aligned(quotient_terms_table_bytes(false));
+  SV_TRY(ws->reserve(tb));
+  SV_TRY(ws->reserve_pinned(tb + 256));
+  SV_TRY(permutation_terms_enqueue(call, ws->buf, ws->pinned, ws->stream));
+  return terms_finish(&dl, tb);
+  SV_GUARD_END
+}
+
+int sv_bn254_fr_lookup_terms_device(const sv_fr_lookup* lookups, size_t n_lookups, const sv_fe* d_l0,
+                                    const sv_fe* d_l_last, const sv_fe* d_l_active, const sv_fe* beta,
+                                    const sv_fe* gamma, const sv_fe* y, const sv_fe* d_acc_in, sv_fe* d_out,
+                                    uint32_t log_n, uint32_t log_ext, int form, int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  const TermsCommon c{d_l0, d_l_last, d_l_active, beta, gamma, y, d_acc_in, d_out, log_n, log_ext};
+  SV_TRY(terms_null_rules(c));
+  if (!lookups) {
+    sv::set_error("null pointer (lookup descriptors)");
+    return SV_ERR_ARG;
+  }
+  const size_t seen = std::min(n_lookups, (size_t)SV_TERMS_LOOKUPS_MAX);  // descriptors beyond the cap are not looked at
+  uintptr_t bits = 0;
+  for (size_t l = 0; l < seen; l++) {
+    const sv_fr_lookup& d = lookups[l];
+    if (!d.d_z || !d.d_permuted_input || !d.d_permuted_table || !d.d_input || !d.d_table) {
+      sv::set_error("null pointer (lookup %zu)", l);
+      return SV_ERR_ARG;
+    }
+    bits |= (uintptr_t)d.d_z | (uintptr_t)d.d_permuted_input | (uintptr_t)d.d_permuted_table | (uintptr_t)d.d_input |
+            (uintptr_t)d.d_table;
+  }
+  if (bits & 15u) {
+    sv::set_error("the lookup columns must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  SV_TRY(terms_align_rules(c));
+  if (n_lookups == 0) {
+    sv::set_error("the lookups should not be empty (n_lookups == 0)");
+    return SV_ERR_EMPTY;
+  }
+  SV_TRY(terms_size_rules(c, n_lookups, SV_TERMS_LOOKUPS_MAX, "lookups"));
+  SV_TRY(terms_scalar_rules(c));
+  SV_TRY(terms_overlap_rules(c));
+  for (size_t l = 0; l < n_lookups; l++) {
+    const sv_fr_lookup& d = lookups[l];
+    SV_TRY(terms_overlap_rule(c, d.d_z));
+    SV_TRY(terms_overlap_rule(c, d.d_permuted_input));
+    SV_TRY(terms_overlap_rule(c, d.d_permuted_table));
+    SV_TRY(terms_overlap_rule(c, d.d_input));
+    SV_TRY(terms_overlap_rule(c, d.d_table));
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  QtLookupCall call{};
+  call.lookups = lookups, call.n_lookups = n_lookups;
+  call.d_l0 = d_l0, call.d_l_last = d_l_last, call.d_l_active = d_l_active;
+  call.beta = *beta, call.gamma = *gamma, call.y = *y;
+  call.d_acc_in = d_acc_in, call.d_out = d_out;
+  call.log_n = log_n, call.log_ext = log_ext;
+  call.form = form;
+  const size_t tb = Workspace::aligned(quotient_terms_table_bytes(true));
+  SV_TRY(ws->reserve(tb));
+  SV_TRY(ws->reserve_pinned(tb + 256));
+  SV_TRY(lookup_terms_enqueue(call, ws->buf, ws->pinned, ws->stream));
+  return terms_finish(&dl, tb);
   SV_GUARD_END
 }
 

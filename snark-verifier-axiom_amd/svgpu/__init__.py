@@ -149,6 +149,39 @@ def lookup_product(inputs, tables, permuted_input, permuted_table, beta, gamma, 
     return grand_product_device(num, den, z0=z0, **kwargs)
 
 
+def permutation_terms_device(cols, sigmas, s, chunk, z, l0, l_last, l_active, beta, gamma, y, log_n,
+                             last_rotation, **kwargs):
+    """svgpu.device.permutation_terms_device (imported on first use: that module needs torch)."""
+    from .device import permutation_terms_device as run
+    return run(cols, sigmas, s, chunk, z, l0, l_last, l_active, beta, gamma, y, log_n, last_rotation, **kwargs)
+
+
+def lookup_terms_device(lookups, l0, l_last, l_active, beta, gamma, y, log_n, **kwargs):
+    """svgpu.device.lookup_terms_device (imported on first use: that module needs torch)."""
+    from .device import lookup_terms_device as run
+    return run(lookups, l0, l_last, l_active, beta, gamma, y, log_n, **kwargs)
+
+
+def lagrange_selectors_device(k, log_ext, blinding, **kwargs):
+    """svgpu.device.lagrange_selectors_device (imported on first use: that module needs torch)."""
+    from .device import lagrange_selectors_device as run
+    return run(k, log_ext, blinding, **kwargs)
+
+
+def permutation_terms(values, sigmas, z, chunk, l0, l_last, l_active, beta, gamma, y, delta, log_n,
+                      last_rotation, **kwargs):
+    """permutation_terms_device with s_j = beta delta^j built here, as permutation_factors builds it
+    for the grand product: values and sigmas are all m permutation columns on the extended domain,
+    z the ceil(m / chunk) running products, delta the domain's coset generator (a canonical int)."""
+    from .encoding import R
+    s, d = [], 1
+    for _ in values:
+        s.append(beta * d % R)
+        d = d * delta % R
+    return permutation_terms_device(values, sigmas, s, chunk, z, l0, l_last, l_active, beta, gamma, y, log_n,
+                                    last_rotation, **kwargs)
+
+
 def sort_device(data, **kwargs):
     """svgpu.device.sort_device (imported on first use: that module needs torch)."""
     from .device import sort_device as run

@@ -25,6 +25,8 @@ SV_NTT_MAX_LOG = 26        # log2 of the longest transform
 SV_NTT_FORWARD = 0
 SV_NTT_INVERSE = 1
 SV_EXT_LOG_MAX = 8         # log2 of the widest extension of coset_lde / quotient_coeffs
+SV_TERMS_COLUMNS_MAX = 64  # permutation columns (and z columns) per permutation_terms call
+SV_TERMS_LOOKUPS_MAX = 16  # lookups per lookup_terms call
 
 SV_FACTOR_PLAIN = 0        # f[i] = x[i] + c
 SV_FACTOR_COLUMN = 1       # f[i] = x[i] + s*y[i] + c
@@ -93,6 +95,11 @@ class sv_shplonk_set(Structure):
 
 class sv_fr_factor(Structure):
     _fields_ = [("d_x", c_void_p), ("d_y", c_void_p), ("s", sv_fe), ("c", sv_fe), ("kind", c_uint32)]
+
+
+class sv_fr_lookup(Structure):
+    _fields_ = [("d_z", c_void_p), ("d_permuted_input", c_void_p), ("d_permuted_table", c_void_p),
+                ("d_input", c_void_p), ("d_table", c_void_p)]
 
 
 class sv_msm_stats(Structure):
@@ -168,6 +175,13 @@ PROTOTYPES = [
                                               c_int, c_void_p]),
     ("sv_bn254_fr_quotient_coeffs_device", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_size_t, c_void_p,
                                                     c_int, c_int, c_void_p]),
+    ("sv_bn254_fr_permutation_terms_device", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
+                                                      c_void_p, c_void_p, c_void_p, POINTER(sv_fe), POINTER(sv_fe),
+                                                      POINTER(sv_fe), POINTER(sv_fe), c_int32, c_void_p, c_void_p,
+                                                      c_uint32, c_uint32, c_int, c_int, c_void_p]),
+    ("sv_bn254_fr_lookup_terms_device", c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, POINTER(sv_fe),
+                                                 POINTER(sv_fe), POINTER(sv_fe), c_void_p, c_void_p, c_uint32, c_uint32,
+                                                 c_int, c_int, c_void_p]),
     ("sv_bn254_fr_grand_product_device", c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, POINTER(sv_fe),
                                                   POINTER(sv_fe), c_int, c_void_p, POINTER(sv_fe), c_int, c_void_p]),
     ("sv_bn254_fr_batch_invert_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

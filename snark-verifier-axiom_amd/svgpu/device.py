@@ -427,6 +427,142 @@ def lookup_permute_device(inputs: torch.Tensor, tables: torch.Tensor, form: int 
     return out[0], out[1]
 
 
+def _terms_column(t: torch.Tensor, n: int, dev, who: str, what: str) -> torch.Tensor:
+    """_column for the terms calls: an (N, 4) int64 tensor on the call's device, made contiguous."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 4:
+        raise _lib.ArgumentError(f"{who}: {what} is an (N, 4) int64 tensor of limbs")
+    if t.device != dev:
+        raise _lib.ArgumentError(f"{who}: the columns of a call live on one device")
+    if t.shape[0] != n:
+        raise _lib.LengthError(f"{who}: {what} has {t.shape[0]} rows, the call {n}")
+    return t.contiguous()
+
+
+def _terms_shape(first: torch.Tensor, log_n: int, who: str) -> Tuple[int, int]:
+    """(N, log_ext) of a terms call from its first column and the circuit's log_n."""
+    if not isinstance(first, torch.Tensor) or first.dim() != 2:
+        raise _lib.ArgumentError(f"{who}: a column is an (N, 4) int64 tensor of limbs")
+    N = first.shape[0]
+    if N == 0 or N & (N - 1):
+        raise _lib.LengthError(f"{who}: {N} rows is not a power of two")
+    K = N.bit_length() - 1
+    if not 0 <= log_n <= K:
+        raise _lib.LengthError(f"{who}: log_n = {log_n} is not in 0 .. {K}")
+    return N, K - log_n
+
+
+def _terms_out(out, acc, N: int, dev, who: str):
+    """The accumulator (or None) and the output of a terms call; out=None allocates, out=acc is in place."""
+    if acc is not None:
+        acc = _terms_column(acc, N, dev, who, "acc")
+    if out is None:
+        out = torch.empty((N, 4), dtype=torch.int64, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.int64
+          or not out.is_contiguous() or tuple(out.shape) != (N, 4)):
+        raise _lib.LengthError(f"{who}: out must be a contiguous ({N}, 4) int64 tensor on {dev}")
+    return acc, out
+
+
+def _pointer_array(tensors):
+    arr = (ctypes.c_void_p * max(len(tensors), 1))()
+    for j, t in enumerate(tensors):
+        arr[j] = t.data_ptr()
+    return arr
+
+
+def permutation_terms_device(cols, sigmas, s, chunk: int, z, l0: torch.Tensor, l_last: torch.Tensor,
+                             l_active: torch.Tensor, beta: int, gamma: int, y: int, log_n: int,
+                             last_rotation: int, shift: Optional[int] = None, acc: torch.Tensor = None,
+                             form: int = _lib.SV_MONTGOMERY, out: torch.Tensor = None) -> torch.Tensor:
+    """The permutation argument's constraints (system/halo2.rs:501-591) on HBM-resident extended
+    columns ((N, 4) int64 limbs in `form`, N = 2^(log_n + log_ext), row j at shift omega_K^j), folded in
+    y onto `acc` (None = 0): per constraint c, acc <- acc y + c.  cols and sigmas are the m permutation
+    columns and their sigmas, s the m canonical ints beta delta^j, z the ceil(m / chunk) running
+    products; l0, l_last, l_active the selector columns; last_rotation = -(blinding + 1).  beta,
+    gamma, y and shift (None = 1) are canonical ints.  out=None allocates, out=acc is in place; any
+    other `out` (N rows) must not overlap an input."""
+    who = "permutation_terms"
+    cols, sigmas, z, s = list(cols), list(sigmas), list(z), list(s)
+    if not cols:
+        raise _lib.EmptyError(f"{who}: no permutation columns")
+    if chunk < 1:
+        raise _lib.ArgumentError(f"{who}: chunk = {chunk}: a z column covers at least one permutation column")
+    if not len(cols) == len(sigmas) == len(s):
+        raise _lib.LengthError(f"{who}: cols, sigmas and s differ in length")
+    m = len(cols)
+    if len(z) != -(-m // chunk):
+        raise _lib.LengthError(f"{who}: {len(z)} z columns, {m} columns in chunks of {chunk} need {-(-m // chunk)}")
+    N, log_ext = _terms_shape(cols[0], log_n, who)
+    d, dev = _dev_index(cols[0]), cols[0].device
+    cols = [_terms_column(t, N, dev, who, "a column") for t in cols]
+    sigmas = [_terms_column(t, N, dev, who, "a sigma") for t in sigmas]
+    z = [_terms_column(t, N, dev, who, "a z") for t in z]
+    l0, l_last, l_active = (_terms_column(t, N, dev, who, "an l column") for t in (l0, l_last, l_active))
+    acc, out = _terms_out(out, acc, N, dev, who)
+    bs, gs, ys = enc.fr_struct(beta, form), enc.fr_struct(gamma, form), enc.fr_struct(y, form)
+    sh = enc.fr_struct(shift, form) if shift is not None else None
+    _lib.check(_lib.lib.sv_bn254_fr_permutation_terms_device(
+        _pointer_array(cols), _pointer_array(sigmas), fe_array(s, form), m, chunk, _pointer_array(z),
+        l0.data_ptr(), l_last.data_ptr(), l_active.data_ptr(), ctypes.byref(bs), ctypes.byref(gs), ctypes.byref(ys),
+        ctypes.byref(sh) if sh is not None else None, last_rotation, acc.data_ptr() if acc is not None else None,
+        out.data_ptr(), log_n, log_ext, form, d, _stream_handle(dev)), "sv_bn254_fr_permutation_terms_device")
+    return out
+
+
+def lookup_terms_device(lookups, l0: torch.Tensor, l_last: torch.Tensor, l_active: torch.Tensor, beta: int,
+                        gamma: int, y: int, log_n: int, acc: torch.Tensor = None, form: int = _lib.SV_MONTGOMERY,
+                        out: torch.Tensor = None) -> torch.Tensor:
+    """Each lookup's five constraints (system/halo2.rs:593-655) on HBM-resident extended columns ((N,
+    4) int64 limbs in `form`), folded in y onto `acc` (None = 0).  lookups is a list of (z,
+    permuted_input, permuted_table, input, table); l0, l_last, l_active the selector columns; beta,
+    gamma, y canonical ints.  out=None allocates, out=acc is in place; any other `out` (N rows) must
+    not overlap an input."""
+    who = "lookup_terms"
+    lookups = [tuple(lk) for lk in lookups]
+    if not lookups:
+        raise _lib.EmptyError(f"{who}: no lookups")
+    if any(len(lk) != 5 for lk in lookups):
+        raise _lib.ArgumentError(f"{who}: a lookup is (z, permuted_input, permuted_table, input, table)")
+    first = lookups[0][0]
+    N, log_ext = _terms_shape(first, log_n, who)
+    d, dev = _dev_index(first), first.device
+    lookups = [tuple(_terms_column(t, N, dev, who, "a lookup column") for t in lk) for lk in lookups]
+    l0, l_last, l_active = (_terms_column(t, N, dev, who, "an l column") for t in (l0, l_last, l_active))
+    acc, out = _terms_out(out, acc, N, dev, who)
+    arr = (_lib.sv_fr_lookup * len(lookups))()
+    for j, lk in enumerate(lookups):
+        (arr[j].d_z, arr[j].d_permuted_input, arr[j].d_permuted_table, arr[j].d_input,
+         arr[j].d_table) = (t.data_ptr() for t in lk)
+    bs, gs, ys = enc.fr_struct(beta, form), enc.fr_struct(gamma, form), enc.fr_struct(y, form)
+    _lib.check(_lib.lib.sv_bn254_fr_lookup_terms_device(
+        arr, len(lookups), l0.data_ptr(), l_last.data_ptr(), l_active.data_ptr(), ctypes.byref(bs), ctypes.byref(gs),
+        ctypes.byref(ys), acc.data_ptr() if acc is not None else None, out.data_ptr(), log_n, log_ext, form, d,
+        _stream_handle(dev)), "sv_bn254_fr_lookup_terms_device")
+    return out
+
+
+def lagrange_selectors_device(k: int, log_ext: int, blinding: int, shift: Optional[int] = None,
+                              form: int = _lib.SV_MONTGOMERY, device=None):
+    """The selector columns of the zk quotient on the extended domain, (l0, l_last, l_active,
+    last_rotation): with n = 2^k and u = n - blinding - 1 the last usable row, l0 is the Lagrange
+    polynomial of row 0, l_last that of row u, l_active the indicator of rows [0, u), each as (2^(k +
+    log_ext), 4) limbs in `form` at shift omega_K^j; last_rotation = -(blinding + 1).  Built from the
+    three indicator columns through ntt_device(inverse=True) and coset_lde_device with count 3."""
+    n = 1 << k
+    if blinding < 0 or blinding + 1 >= n:
+        raise _lib.LengthError(f"lagrange_selectors: blinding = {blinding} leaves no usable row of {n}")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    u = n - blinding - 1
+    one = np.asarray(enc.scalars_array([1], form)).view(np.int64).reshape(4)
+    ind = np.zeros((3, n, 4), np.int64)
+    ind[0, 0] = one
+    ind[1, u] = one
+    ind[2, :u] = one
+    coeffs = ntt_device(torch.from_numpy(ind).to(dev), inverse=True, form=form)
+    ext = coset_lde_device(coeffs, log_ext, shift=shift, form=form)
+    return ext[0], ext[1], ext[2], -(blinding + 1)
+
+
 def last_msm_stats() -> dict:
     s = _lib.sv_msm_stats()
     _lib.check(_lib.lib.sv_msm_last_stats(ctypes.byref(s)), "sv_msm_last_stats")

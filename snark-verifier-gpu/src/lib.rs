@@ -94,6 +94,20 @@ pub const SV_NTT_FORWARD: c_int = 0;
 pub const SV_NTT_INVERSE: c_int = 1;
 /// log2 of the widest extension sv_bn254_fr_coset_lde_device / _quotient_coeffs_device take.
 pub const SV_EXT_LOG_MAX: u32 = 8;
+/// Permutation columns (and so z columns) per sv_bn254_fr_permutation_terms_device call.
+pub const SV_TERMS_COLUMNS_MAX: usize = 64;
+/// Lookups per sv_bn254_fr_lookup_terms_device call.
+pub const SV_TERMS_LOOKUPS_MAX: usize = 16;
+/// sv_fr_lookup: the five extended columns of one lookup (z, a', s', A, S), all in HBM.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SvFrLookup {
+    pub d_z: *const SvFe,
+    pub d_permuted_input: *const SvFe,
+    pub d_permuted_table: *const SvFe,
+    pub d_input: *const SvFe,
+    pub d_table: *const SvFe,
+}
 /// sv_fr_factor: one factor of a grand product; `kind` is one of the SV_FACTOR_* values.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -222,6 +236,22 @@ extern "C" {
     pub fn sv_bn254_fr_quotient_coeffs_device(d_numer: *const SvFe, d_out: *mut SvFe, log_n: u32, log_ext: u32,
                                               pieces: usize, shift: *const SvFe, form: c_int, device: c_int,
                                               stream: *mut c_void) -> c_int;
+    /// The permutation argument's constraints on extended columns in HBM, folded in y onto d_acc_in
+    /// (null = 0) into d_out; pointer arrays and scalars are host pointers (`shift` null = 1).
+    pub fn sv_bn254_fr_permutation_terms_device(d_cols: *const *const SvFe, d_sigmas: *const *const SvFe,
+                                                s: *const SvFe, m: usize, chunk: usize, d_z: *const *const SvFe,
+                                                d_l0: *const SvFe, d_l_last: *const SvFe, d_l_active: *const SvFe,
+                                                beta: *const SvFe, gamma: *const SvFe, y: *const SvFe,
+                                                shift: *const SvFe, last_rotation: i32, d_acc_in: *const SvFe,
+                                                d_out: *mut SvFe, log_n: u32, log_ext: u32, form: c_int,
+                                                device: c_int, stream: *mut c_void) -> c_int;
+    /// Each lookup's five constraints on extended columns in HBM, folded in y onto d_acc_in (null = 0)
+    /// into d_out; the descriptors and scalars are host pointers.
+    pub fn sv_bn254_fr_lookup_terms_device(lookups: *const SvFrLookup, n_lookups: usize, d_l0: *const SvFe,
+                                           d_l_last: *const SvFe, d_l_active: *const SvFe, beta: *const SvFe,
+                                           gamma: *const SvFe, y: *const SvFe, d_acc_in: *const SvFe,
+                                           d_out: *mut SvFe, log_n: u32, log_ext: u32, form: c_int, device: c_int,
+                                           stream: *mut c_void) -> c_int;
     /// Running product z[0] = z0, z[i + 1] = z[i] num(i) / den(i) over columns in HBM; descriptor arrays
     /// and z0 / omega / out_total are host pointers (omega, out_total may be null).
     pub fn sv_bn254_fr_grand_product_device(num: *const SvFrFactor, n_num: usize, den: *const SvFrFactor,
