@@ -429,8 +429,8 @@ int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size
 /* ---- extended-domain quotient: coset LDE and division by X^n - 1 ---------------------------
  * The two fixed-function ends of a halo2 prover's quotient, for data that is already in HBM:
  * EvaluationDomain::coeff_to_extended going in, and divide_by_vanishing_poly, extended_to_coeff and
- * the h_pieces of vanishing::Argument::construct coming out.  The gate arithmetic between the two
- * is the caller's.  Throughout n = 2^log_n, K = log_n + log_ext, omega_K = root_of_unity(K),
+ * the h_pieces of vanishing::Argument::construct coming out.  The numerator between the two is the
+ * next two blocks'.  Throughout n = 2^log_n, K = log_n + log_ext, omega_K = root_of_unity(K),
  * omega_e = omega_K^n = root_of_unity(log_ext), g = *shift (a host pointer, in `form`).  The library
  * holds no zeta, as it holds no delta: a halo2 caller passes g = Fr::ZETA = 7^((r - 1) / 3).
  * fr_coset_lde_device: `count` polynomials of exactly n coefficients each lie back to back in
@@ -466,9 +466,8 @@ int sv_bn254_fr_ntt_device(const sv_fe* d_in, sv_fe* d_out, uint32_t log_n, size
  * Scratch (pooled): the NTT's at K -- 256 B, the first pass's flags and, with two or more passes
  * (K > 10), one image of count 2^K elements -- plus, for the quotient, the table (2^log_ext x 32 B)
  * and as many bytes of pinned host memory for its one small copy on the call's stream.
- * Not covered: custom gate expressions of the numerator (its permutation and lookup terms: the
- * next block); blinding of h; host buffers; multi-device columns; several quotients per
- * call; a check that the dropped high coefficients are zero.                                   */
+ * Not covered: blinding of h; host buffers; multi-device columns; several quotients per call; a
+ * check that the dropped high coefficients are zero.                                          */
 #define SV_EXT_LOG_MAX 8
 int sv_bn254_fr_coset_lde_device(const sv_fe* d_coeffs, sv_fe* d_evals, uint32_t log_n,
                                  uint32_t log_ext, size_t count, const sv_fe* shift, int form,
@@ -489,7 +488,8 @@ int sv_bn254_fr_quotient_coeffs_device(const sv_fe* d_numer, sv_fe* d_out, uint3
  * columns and every scalar.
  * Both calls continue one fold: acc starts as d_acc_in[j] (0 when d_acc_in is NULL), every
  * constraint c in the order listed does acc <- acc y + c[j], and d_out[j] = acc.  The gate
- * constraints come first in the reference, so a caller folds them into d_acc_in itself; a circuit
+ * constraints come first in the reference: fr_expressions_device (the next block) folds them into
+ * what a caller passes here as d_acc_in; a circuit
  * with more columns or lookups than a call takes calls again on the running accumulator.  d_out ==
  * d_acc_in is in place; any other overlap of d_out with an input column is "overlaps".  Only the zk
  * form of the reference (zk == true) is built.
@@ -532,8 +532,7 @@ int sv_bn254_fr_quotient_coeffs_device(const sv_fe* d_numer, sv_fe* d_out, uint3
  * Each call is one launch (csrc/quotient_terms.hip) that writes d_out once and holds nothing per
  * row outside registers.  Pooled scratch: the call's table of column pointers, s_j and powers of y
  * (under 9 KiB) and as many bytes of pinned host memory for its one small copy on the call's stream.
- * Not covered: custom gate expressions (they enter through d_acc_in); the non-zk variant; the
- * theta-compression of several columns into A and S; host buffers; multi-device columns.        */
+ * Not covered: the non-zk variant; host buffers; multi-device columns.                          */
 #define SV_TERMS_COLUMNS_MAX 64   /* permutation columns per call, and so z columns */
 #define SV_TERMS_LOOKUPS_MAX 16   /* lookups per call */
 typedef struct { const sv_fe* d_z; const sv_fe* d_permuted_input; const sv_fe* d_permuted_table;
@@ -553,6 +552,88 @@ int sv_bn254_fr_lookup_terms_device(const sv_fr_lookup* lookups, size_t n_lookup
                                     const sv_fe* y, const sv_fe* d_acc_in, sv_fe* d_out,
                                     uint32_t log_n, uint32_t log_ext, int form, int device,
                                     void* stream) SV_NOEXCEPT;
+
+/* ---- expression programs: custom gates and theta-compression ------------------------------
+ * The two steps of the quotient pipeline that are a circuit's own: its gate constraints (the
+ * reference's gate_constraints, snark-verifier/src/system/halo2.rs:451-455, which come FIRST in the
+ * fold of :657-668) and the theta-compression of a lookup's input and table expressions into A and
+ * S (compress, :614-619).  Both evaluate trees of the reference's Expression<F>
+ * (snark-verifier/src/verifier/plonk/protocol.rs:309-370) at every row of a set of columns; here a
+ * tree is a flat postfix program over an operand stack, evaluated independently at every row j < N.
+ * Notation as in the block above: n = 2^log_n, N = 2^(log_n + log_ext), E = 2^log_ext, rot(c, r)[j] =
+ * c[(j + r E) mod N], r of either sign.  log_ext = 0 is the original domain, where theta-compression
+ * runs.  d_cols[i], i < n_cols, and d_stores[k], k < n_stores, are N elements each in HBM on
+ * `device`; the program, the pointer arrays, consts and y are host memory; `form` covers the
+ * columns, the constants and y.
+ * An op is { op, zero = 0, index, rotation }: index names the column (COLUMN), constant (CONST) or
+ * store (STORE) and is 0 otherwise; rotation is r for COLUMN and 0 otherwise.  With b the top:
+ *     COLUMN        -> rot(d_cols[index], rotation)[j]      CONST      -> consts[index]
+ *     NEG    a      -> -a                                   ADD   a b  -> a + b
+ *     SUB    a b    -> a - b                                RSUB  a b  -> b - a
+ *     MUL    a b    -> a b
+ *     FOLD   v      -> (nothing);  acc <- acc y + v         STORE v    -> (nothing);  d_stores[index][j] = v
+ * acc starts as d_acc_in[j] (0 when d_acc_in is NULL) and, if the program has at least one FOLD,
+ * d_out[j] = acc is written once at the end: the running accumulator of the two terms calls, so a
+ * caller runs its gates through this call and passes d_out on as their d_acc_in.  d_out == d_acc_in
+ * is in place.  A program with no FOLD reads none of y, d_acc_in, d_out: they may be NULL.  Each
+ * store index is the target of at most one STORE.  The reference's variants map one to one:
+ * Constant and Challenge are CONST (values in `form`), Polynomial(Query) is COLUMN, Negated NEG, Sum
+ * ADD, Product MUL, Scaled is CONST then MUL, DistributePowers is the Horner chain of
+ * protocol.rs:359-368 written with MUL and ADD, and a CommonPolynomial (l_0, l_last, l_active, X) is
+ * a column the caller supplies (X_j is the coset LDE of the polynomial X).  SUB and RSUB let a
+ * compiler evaluate the deeper operand first.
+ * Checked before any device work, in this order (entries beyond a cap are not looked at):
+ *   1. bad form                                                                        SV_ERR_ARG
+ *   2. a null program, d_cols (n_cols > 0), consts (n_consts > 0), d_stores (n_stores > 0)
+ *      or entry of either pointer array                                                SV_ERR_ARG
+ *   3. a column, store, d_acc_in or d_out not 16-byte aligned                          SV_ERR_ARG
+ *   4. n_ops == 0                                                                      SV_ERR_EMPTY
+ *   5. log_ext > SV_EXT_LOG_MAX, K > SV_NTT_MAX_LOG, then n_ops, n_cols, n_consts or
+ *      n_stores above its cap                                                          SV_ERR_LEN
+ *   6. the program, op by op, the message naming the first offending op: an unknown opcode; a
+ *      non-zero `zero` field; an index out of range for its table (non-zero on an op without
+ *      one); a rotation outside -n < r < n; a non-zero rotation on any op but COLUMN; stack
+ *      underflow; depth above SV_EXPR_STACK_MAX; a second STORE to one index; then, at the end,
+ *      a non-empty stack; a program with neither FOLD nor STORE                        SV_ERR_ARG
+ *   7. a FOLD in the program with y or d_out NULL                                      SV_ERR_ARG
+ *   8. y or a constant that the program reads not below r             SV_ERR_ARG ("not reduced")
+ *   9. a store that is written, or d_out, overlapping anything else passed to the call: a
+ *      column, d_acc_in (the exact d_out == d_acc_in apart), another store: an output row is
+ *      written while other threads still read rotated rows           SV_ERR_ARG ("overlaps")
+ * An element not below r in a column the program reads (d_acc_in included) is found on the device
+ * and is SV_ERR_ARG ("not reduced") for that call: the outputs are then unspecified, nothing outside
+ * them is written, and the next call is exact.  A column the program never names is never
+ * dereferenced.  Points 1 and 2 of "Streams" apply (ordered after `stream`, synchronous);
+ * re-entrant from any number of threads.  All mod r: every output is determined bit for bit.
+ * Each call is one launch (csrc/expressions.hip): one thread per row, the top of the operand stack
+ * in registers and the rest in LDS, nothing per row in scratch.  Pooled scratch: the call's table
+ * of pointers, constants, y and ops (under 45 KiB) and as many bytes of pinned host memory for its
+ * one small copy on the call's stream.
+ * Not covered: shared intermediates (no opcode keeps a value for a second use, squares or doubles:
+ * a common subexpression is evaluated again, or stored and read back as a column by a second
+ * call); host buffers; multi-device columns; the non-zk variant.                               */
+enum { SV_EXPR_COLUMN = 0,  /* push d_cols[index][(j + rotation E) mod N]            */
+       SV_EXPR_CONST  = 1,  /* push consts[index]  (constants and challenges alike)  */
+       SV_EXPR_NEG    = 2,  /* a        -> -a                                        */
+       SV_EXPR_ADD    = 3,  /* a b      -> a + b      (b is the top)                 */
+       SV_EXPR_SUB    = 4,  /* a b      -> a - b                                     */
+       SV_EXPR_RSUB   = 5,  /* a b      -> b - a                                     */
+       SV_EXPR_MUL    = 6,  /* a b      -> a b                                       */
+       SV_EXPR_FOLD   = 7,  /* v        -> (nothing);  acc <- acc y + v              */
+       SV_EXPR_STORE  = 8 };/* v        -> (nothing);  d_stores[index][j] = v        */
+typedef struct { uint8_t op; uint8_t zero; uint16_t index; int32_t rotation; } sv_fr_expr_op; /* 8 B */
+#define SV_EXPR_OPS_MAX     4096
+#define SV_EXPR_COLUMNS_MAX 256
+#define SV_EXPR_CONSTS_MAX  256
+#define SV_EXPR_STORES_MAX  16
+#define SV_EXPR_STACK_MAX   8
+int sv_bn254_fr_expressions_device(const sv_fr_expr_op* program, size_t n_ops,
+                                   const sv_fe* const* d_cols, size_t n_cols,
+                                   const sv_fe* consts, size_t n_consts,
+                                   sv_fe* const* d_stores, size_t n_stores,
+                                   const sv_fe* y, const sv_fe* d_acc_in, sv_fe* d_out,
+                                   uint32_t log_n, uint32_t log_ext, int form,
+                                   int device, void* stream) SV_NOEXCEPT;
 
 /* ---- running products and batch inversion over Fr columns in HBM -----------------------
  * The running-product columns of a halo2 prover: the permutation argument's z (one per chunk of
@@ -645,8 +726,7 @@ int sv_bn254_fr_batch_invert_device(const sv_fe* d_in, sv_fe* d_out, size_t n, i
  * synchronous); re-entrant from any number of threads.  Pooled scratch per row: 65 B for a sort
  * (two canonical images and the per-block digit counts), 145 B for a permutation (four images, four
  * u32 lists, the counts): 9.1 GiB at n = 2^26.
- * Not covered: the theta-compression of several columns into A and S; the blinding rows; host
- * buffers; multi-device columns.                                                              */
+ * Not covered: the blinding rows; host buffers; multi-device columns.                          */
 int sv_bn254_fr_sort_device(const sv_fe* d_in, sv_fe* d_out, size_t n, int form, int device,
                             void* stream) SV_NOEXCEPT;
 int sv_bn254_fr_lookup_permute_device(const sv_fe* d_input, const sv_fe* d_table, size_t n,

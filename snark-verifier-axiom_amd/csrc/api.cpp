@@ -29,6 +29,7 @@
 #include "ntt.hpp"
 #include "poseidon.hpp"
 #include "quotient_terms.hpp"
+#include "expressions.hpp"
 #include "runtime.hpp"
 
 using namespace sv;
@@ -2539,6 +2540,145 @@ int sv_bn254_fr_lookup_terms_device(const sv_fr_lookup* lookups, size_t n_lookup
   SV_TRY(ws->reserve(tb));
   SV_TRY(ws->reserve_pinned(tb + 256));
   SV_TRY(lookup_terms_enqueue(call, ws->buf, ws->pinned, ws->stream));
+  return terms_finish(&dl, tb);
+  SV_GUARD_END
+}
+
+// ---- expression programs: custom gates and theta-compression (csrc/expressions.hip) ----
+namespace {
+static_assert(sizeof(sv_fr_expr_op) == sizeof(ExprOp) && offsetof(sv_fr_expr_op, op) == offsetof(ExprOp, op) &&
+                  offsetof(sv_fr_expr_op, zero) == offsetof(ExprOp, zero) &&
+                  offsetof(sv_fr_expr_op, index) == offsetof(ExprOp, index) &&
+                  offsetof(sv_fr_expr_op, rotation) == offsetof(ExprOp, rotation),
+              "expr_plan.hpp walks the ABI's ops");
+static_assert(SV_EXPR_COLUMN == kExprColumn && SV_EXPR_CONST == kExprConst && SV_EXPR_NEG == kExprNeg &&
+                  SV_EXPR_ADD == kExprAdd && SV_EXPR_SUB == kExprSub && SV_EXPR_RSUB == kExprRsub &&
+                  SV_EXPR_MUL == kExprMul && SV_EXPR_FOLD == kExprFold && SV_EXPR_STORE == kExprStore,
+              "expr_plan.hpp's opcodes are the header's");
+static_assert(SV_EXPR_OPS_MAX == kExprOpsMax && SV_EXPR_COLUMNS_MAX == kExprColumnsMax &&
+                  SV_EXPR_CONSTS_MAX == kExprConstsMax && SV_EXPR_STORES_MAX == kExprStoresMax &&
+                  SV_EXPR_STACK_MAX == kExprStackMax,
+              "expr_plan.hpp's caps are the header's");
+
+// rule 9 for one output against one other range of the call
+int expr_overlap_rule(const void* out, const char* what, const void* other, size_t bytes) {
+  if (ranges_overlap(out, other, bytes)) {
+    sv::set_error("%s overlaps something else passed to the call (in place is d_out == d_acc_in only)", what);
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
+}
+}  // namespace
+
+int sv_bn254_fr_expressions_device(const sv_fr_expr_op* program, size_t n_ops, const sv_fe* const* d_cols,
+                                   size_t n_cols, const sv_fe* consts, size_t n_consts, sv_fe* const* d_stores,
+                                   size_t n_stores, const sv_fe* y, const sv_fe* d_acc_in, sv_fe* d_out,
+                                   uint32_t log_n, uint32_t log_ext, int form, int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  SV_TRY(check_form(form));
+  if (!program || (n_cols && !d_cols) || (n_consts && !consts) || (n_stores && !d_stores)) {
+    sv::set_error("null pointer (program, d_cols, consts or d_stores)");
+    return SV_ERR_ARG;
+  }
+  // entries beyond a cap are not looked at
+  const size_t seen_cols = std::min(n_cols, (size_t)SV_EXPR_COLUMNS_MAX);
+  const size_t seen_stores = std::min(n_stores, (size_t)SV_EXPR_STORES_MAX);
+  uintptr_t bits = (uintptr_t)d_acc_in | (uintptr_t)d_out;
+  for (size_t j = 0; j < seen_cols; j++) {
+    if (!d_cols[j]) {
+      sv::set_error("null pointer (d_cols[%zu])", j);
+      return SV_ERR_ARG;
+    }
+    bits |= (uintptr_t)d_cols[j];
+  }
+  for (size_t j = 0; j < seen_stores; j++) {
+    if (!d_stores[j]) {
+      sv::set_error("null pointer (d_stores[%zu])", j);
+      return SV_ERR_ARG;
+    }
+    bits |= (uintptr_t)d_stores[j];
+  }
+  if (bits & 15u) {
+    sv::set_error("the columns, the stores, d_acc_in and d_out must be 16-byte aligned");
+    return SV_ERR_ARG;
+  }
+  if (n_ops == 0) {
+    sv::set_error("the program should not be empty (n_ops == 0)");
+    return SV_ERR_EMPTY;
+  }
+  if (log_ext > SV_EXT_LOG_MAX) {
+    sv::set_error("log_ext = %u: beyond log_ext %d", log_ext, SV_EXT_LOG_MAX);
+    return SV_ERR_LEN;
+  }
+  if (log_n > SV_NTT_MAX_LOG || log_n + log_ext > SV_NTT_MAX_LOG) {
+    sv::set_error("log_n = %u, log_ext = %u: beyond 2^%d rows per column", log_n, log_ext, SV_NTT_MAX_LOG);
+    return SV_ERR_LEN;
+  }
+  const struct { size_t count, cap; const char* what; } counts[] = {{n_ops, SV_EXPR_OPS_MAX, "ops"},
+                                                                     {n_cols, SV_EXPR_COLUMNS_MAX, "columns"},
+                                                                     {n_consts, SV_EXPR_CONSTS_MAX, "constants"},
+                                                                     {n_stores, SV_EXPR_STORES_MAX, "stores"}};
+  for (const auto& c : counts)
+    if (c.count > c.cap) {
+      sv::set_error("%zu %s: a call takes at most %zu", c.count, c.what, c.cap);
+      return SV_ERR_LEN;
+    }
+  ExprPlan plan;
+  size_t at = 0;
+  const ExprFault fault = expr_walk(reinterpret_cast<const ExprOp*>(program), n_ops, n_cols, n_consts, n_stores, log_n,
+                                    &plan, &at);
+  if (fault != kExprOk) {
+    if (at < n_ops)
+      sv::set_error("op %zu (opcode %u, index %u, rotation %d): %s", at, (unsigned)program[at].op,
+                    (unsigned)program[at].index, (int)program[at].rotation, expr_fault_text(fault));
+    else
+      sv::set_error("after op %zu, the last: %s", n_ops - 1, expr_fault_text(fault));
+    return SV_ERR_ARG;
+  }
+  if (plan.folds && (!y || !d_out)) {
+    sv::set_error("null pointer (y or d_out of a program that folds)");
+    return SV_ERR_ARG;
+  }
+  if (plan.folds && !fr_reduced(*y)) {
+    sv::set_error("y not reduced mod the scalar field order");
+    return SV_ERR_ARG;
+  }
+  for (size_t j = 0; j < n_consts; j++)
+    if (plan.const_used[j] && !fr_reduced(consts[j])) {
+      sv::set_error("consts[%zu] not reduced mod the scalar field order", j);
+      return SV_ERR_ARG;
+    }
+  const size_t bytes = (size_t(1) << (log_n + log_ext)) * sizeof(sv_fe);
+  for (size_t k = 0; k <= n_stores; k++) {  // the written stores, then d_out
+    const bool is_out = k == n_stores;
+    if (is_out ? !plan.folds : !plan.store_used[k]) continue;
+    const void* o = is_out ? (const void*)d_out : (const void*)d_stores[k];
+    const char* what = is_out ? "d_out" : "a store";
+    for (size_t j = 0; j < n_cols; j++) SV_TRY(expr_overlap_rule(o, what, d_cols[j], bytes));
+    for (size_t j = 0; j < n_stores; j++)
+      if (j != k) SV_TRY(expr_overlap_rule(o, what, d_stores[j], bytes));
+    if (plan.folds && !is_out) SV_TRY(expr_overlap_rule(o, what, d_out, bytes));
+    if (plan.folds && d_acc_in && !(is_out && d_acc_in == d_out)) SV_TRY(expr_overlap_rule(o, what, d_acc_in, bytes));
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  ExprCall call{};
+  call.program = program, call.n_ops = n_ops;
+  call.d_cols = d_cols, call.n_cols = n_cols;
+  call.consts = consts, call.n_consts = n_consts;
+  call.d_stores = d_stores, call.n_stores = n_stores;
+  call.y = y;
+  call.d_acc_in = plan.folds ? d_acc_in : nullptr, call.d_out = d_out;
+  call.log_n = log_n, call.log_ext = log_ext;
+  call.form = form;
+  call.plan = &plan;
+  const size_t tb = Workspace::aligned(expressions_table_bytes(n_ops));
+  SV_TRY(ws->reserve(tb));
+  SV_TRY(ws->reserve_pinned(tb + 256));
+  SV_TRY(expressions_enqueue(call, ws->buf, ws->pinned, ws->stream));
+  static_assert(kExprErrOffset == kQtErrOffset, "terms_finish reads the flag where this table keeps it");
   return terms_finish(&dl, tb);
   SV_GUARD_END
 }

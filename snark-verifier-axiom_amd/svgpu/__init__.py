@@ -162,6 +162,24 @@ def lookup_terms_device(lookups, l0, l_last, l_active, beta, gamma, y, log_n, **
     return run(lookups, l0, l_last, l_active, beta, gamma, y, log_n, **kwargs)
 
 
+def expressions_device(program, cols, consts, stores=(), **kwargs):
+    """svgpu.device.expressions_device (imported on first use: that module needs torch)."""
+    from .device import expressions_device as run
+    return run(program, cols, consts, stores, **kwargs)
+
+
+def compile_expressions(sinks):
+    """svgpu.expr.compile_expressions: expression trees -> (ops, consts, depth) for expressions_device."""
+    from .expr import compile_expressions as run
+    return run(sinks)
+
+
+def compress_expressions(exprs, theta):
+    """svgpu.expr.compress_expressions: the theta-compression of a lookup's expressions as one tree."""
+    from .expr import compress_expressions as run
+    return run(exprs, theta)
+
+
 def lagrange_selectors_device(k, log_ext, blinding, **kwargs):
     """svgpu.device.lagrange_selectors_device (imported on first use: that module needs torch)."""
     from .device import lagrange_selectors_device as run

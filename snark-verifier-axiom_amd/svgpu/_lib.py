@@ -8,7 +8,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_size_t, c_uint8, c_uint16, c_uint32,
+                    c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVGPU_LIB", os.path.join(os.path.dirname(_HERE), "build", "libsvgpu.so"))
@@ -27,6 +28,15 @@ SV_NTT_INVERSE = 1
 SV_EXT_LOG_MAX = 8         # log2 of the widest extension of coset_lde / quotient_coeffs
 SV_TERMS_COLUMNS_MAX = 64  # permutation columns (and z columns) per permutation_terms call
 SV_TERMS_LOOKUPS_MAX = 16  # lookups per lookup_terms call
+
+# opcodes of an expression program (sv_fr_expr_op.op)
+(SV_EXPR_COLUMN, SV_EXPR_CONST, SV_EXPR_NEG, SV_EXPR_ADD, SV_EXPR_SUB, SV_EXPR_RSUB, SV_EXPR_MUL, SV_EXPR_FOLD,
+ SV_EXPR_STORE) = range(9)
+SV_EXPR_OPS_MAX = 4096     # ops per program
+SV_EXPR_COLUMNS_MAX = 256  # columns a program can name
+SV_EXPR_CONSTS_MAX = 256   # constants (and challenges) a program can name
+SV_EXPR_STORES_MAX = 16    # columns a program can write with STORE
+SV_EXPR_STACK_MAX = 8      # the deepest operand stack
 
 SV_FACTOR_PLAIN = 0        # f[i] = x[i] + c
 SV_FACTOR_COLUMN = 1       # f[i] = x[i] + s*y[i] + c
@@ -100,6 +110,10 @@ class sv_fr_factor(Structure):
 class sv_fr_lookup(Structure):
     _fields_ = [("d_z", c_void_p), ("d_permuted_input", c_void_p), ("d_permuted_table", c_void_p),
                 ("d_input", c_void_p), ("d_table", c_void_p)]
+
+
+class sv_fr_expr_op(Structure):
+    _fields_ = [("op", c_uint8), ("zero", c_uint8), ("index", c_uint16), ("rotation", c_int32)]
 
 
 class sv_msm_stats(Structure):
@@ -182,6 +196,9 @@ PROTOTYPES = [
     ("sv_bn254_fr_lookup_terms_device", c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, POINTER(sv_fe),
                                                  POINTER(sv_fe), POINTER(sv_fe), c_void_p, c_void_p, c_uint32, c_uint32,
                                                  c_int, c_int, c_void_p]),
+    ("sv_bn254_fr_expressions_device", c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                c_size_t, POINTER(sv_fe), c_void_p, c_void_p, c_uint32, c_uint32, c_int,
+                                                c_int, c_void_p]),
     ("sv_bn254_fr_grand_product_device", c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, POINTER(sv_fe),
                                                   POINTER(sv_fe), c_int, c_void_p, POINTER(sv_fe), c_int, c_void_p]),
     ("sv_bn254_fr_batch_invert_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

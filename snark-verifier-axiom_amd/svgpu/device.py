@@ -541,6 +541,55 @@ def lookup_terms_device(lookups, l0: torch.Tensor, l_last: torch.Tensor, l_activ
     return out
 
 
+def expressions_device(program, cols, consts, stores=(), y: Optional[int] = None, acc: torch.Tensor = None,
+                       out: torch.Tensor = None, log_n: int = None, form: int = _lib.SV_MONTGOMERY):
+    """A postfix expression program (include/svgpu.h; svgpu.compile_expressions makes one from
+    trees) at every row of HBM-resident columns ((N, 4) int64 limbs in `form`, N = 2^(log_n +
+    log_ext)): custom gates folded in y onto `acc` (None = 0), per FOLD acc <- acc y + v, and columns
+    written by STORE.  program is a list of (op, index, rotation); cols the columns it names by index;
+    consts and y canonical ints; stores the tensors STORE k writes, or an int to allocate that many.
+    out=None allocates when the program folds, out=acc is in place.  Returns (out, stores): out is
+    None for a program without a FOLD."""
+    who = "expressions"
+    program, cols, consts = [tuple(o) for o in program], list(cols), list(consts)
+    if log_n is None:
+        raise _lib.ArgumentError(f"{who}: log_n is required")
+    if any(len(o) != 3 for o in program):
+        raise _lib.ArgumentError(f"{who}: an op is (op, index, rotation)")
+    first = cols[0] if cols else (stores[0] if not isinstance(stores, int) and len(stores) else acc)
+    if first is None:
+        raise _lib.ArgumentError(f"{who}: no column, store or acc tells the number of rows")
+    N, log_ext = _terms_shape(first, log_n, who)
+    d, dev = _dev_index(first), first.device
+    cols = [_terms_column(t, N, dev, who, "a column") for t in cols]
+    if isinstance(stores, int):
+        stores = [torch.empty((N, 4), dtype=torch.int64, device=dev) for _ in range(stores)]
+    stores = list(stores)
+    for t in stores:
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int64 or not t.is_contiguous()
+                or tuple(t.shape) != (N, 4)):
+            raise _lib.LengthError(f"{who}: a store must be a contiguous ({N}, 4) int64 tensor on {dev}")
+    folds = any(o[0] == _lib.SV_EXPR_FOLD for o in program)
+    if folds:
+        if y is None:
+            raise _lib.ArgumentError(f"{who}: a program that folds needs y")
+        acc, out = _terms_out(out, acc, N, dev, who)
+    else:
+        acc = out = None
+    ops = (_lib.sv_fr_expr_op * max(len(program), 1))()
+    for i, (op, index, rotation) in enumerate(program):
+        if not (0 <= op < 256 and 0 <= index < 65536 and -(1 << 31) <= rotation < (1 << 31)):
+            raise _lib.ArgumentError(f"{who}: op {i} = ({op}, {index}, {rotation}) does not fit an op")
+        ops[i].op, ops[i].index, ops[i].rotation = op, index, rotation
+    ys = enc.fr_struct(y, form) if y is not None else None
+    _lib.check(_lib.lib.sv_bn254_fr_expressions_device(
+        ops, len(program), _pointer_array(cols), len(cols), fe_array(consts, form) if consts else None, len(consts),
+        _pointer_array(stores), len(stores), ctypes.byref(ys) if ys is not None else None,
+        acc.data_ptr() if acc is not None else None, out.data_ptr() if out is not None else None, log_n, log_ext,
+        form, d, _stream_handle(dev)), "sv_bn254_fr_expressions_device")
+    return out, stores
+
+
 def lagrange_selectors_device(k: int, log_ext: int, blinding: int, shift: Optional[int] = None,
                               form: int = _lib.SV_MONTGOMERY, device=None):
     """The selector columns of the zk quotient on the extended domain, (l0, l_last, l_active,

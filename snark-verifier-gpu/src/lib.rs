@@ -108,6 +108,36 @@ pub struct SvFrLookup {
     pub d_input: *const SvFe,
     pub d_table: *const SvFe,
 }
+/// sv_fr_expr_op: one op of an expression program (8 bytes); `op` is one of the SV_EXPR_* opcodes, `zero`
+/// stays 0, `index` names the column, constant or store, `rotation` is a COLUMN's rotation in rows of
+/// the original domain.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SvFrExprOp {
+    pub op: u8,
+    pub zero: u8,
+    pub index: u16,
+    pub rotation: i32,
+}
+pub const SV_EXPR_COLUMN: u8 = 0;
+pub const SV_EXPR_CONST: u8 = 1;
+pub const SV_EXPR_NEG: u8 = 2;
+pub const SV_EXPR_ADD: u8 = 3;
+pub const SV_EXPR_SUB: u8 = 4;
+pub const SV_EXPR_RSUB: u8 = 5;
+pub const SV_EXPR_MUL: u8 = 6;
+pub const SV_EXPR_FOLD: u8 = 7;
+pub const SV_EXPR_STORE: u8 = 8;
+/// Ops per program of sv_bn254_fr_expressions_device.
+pub const SV_EXPR_OPS_MAX: usize = 4096;
+/// Columns a program can name.
+pub const SV_EXPR_COLUMNS_MAX: usize = 256;
+/// Constants (and challenges) a program can name.
+pub const SV_EXPR_CONSTS_MAX: usize = 256;
+/// Columns a program can write with STORE.
+pub const SV_EXPR_STORES_MAX: usize = 16;
+/// The deepest operand stack of a program.
+pub const SV_EXPR_STACK_MAX: usize = 8;
 /// sv_fr_factor: one factor of a grand product; `kind` is one of the SV_FACTOR_* values.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -252,6 +282,15 @@ extern "C" {
                                            gamma: *const SvFe, y: *const SvFe, d_acc_in: *const SvFe,
                                            d_out: *mut SvFe, log_n: u32, log_ext: u32, form: c_int, device: c_int,
                                            stream: *mut c_void) -> c_int;
+    /// A postfix expression program at every row of extended columns in HBM: each FOLD joins a value onto
+    /// d_acc_in (null = 0) under y into d_out, the accumulator the two terms calls continue; each STORE
+    /// writes d_stores[index].  The program, the pointer arrays, consts and y are host pointers; y,
+    /// d_acc_in and d_out may be null for a program without a FOLD.
+    pub fn sv_bn254_fr_expressions_device(program: *const SvFrExprOp, n_ops: usize, d_cols: *const *const SvFe,
+                                          n_cols: usize, consts: *const SvFe, n_consts: usize,
+                                          d_stores: *const *mut SvFe, n_stores: usize, y: *const SvFe,
+                                          d_acc_in: *const SvFe, d_out: *mut SvFe, log_n: u32, log_ext: u32,
+                                          form: c_int, device: c_int, stream: *mut c_void) -> c_int;
     /// Running product z[0] = z0, z[i + 1] = z[i] num(i) / den(i) over columns in HBM; descriptor arrays
     /// and z0 / omega / out_total are host pointers (omega, out_total may be null).
     pub fn sv_bn254_fr_grand_product_device(num: *const SvFrFactor, n_num: usize, den: *const SvFrFactor,
