@@ -734,6 +734,55 @@ int sv_bn254_fr_lookup_permute_device(const sv_fe* d_input, const sv_fe* d_table
                                       uint64_t* out_missing_row, int device,
                                       void* stream) SV_NOEXCEPT;
 
+/* ---- Batched lookup permutation: the lookups of a circuit in one call ---------------------
+ * fr_lookup_permute_batch_device: `count` lookups over n usable rows each.  The four pointer
+ *   arrays are HOST arrays of `count` device pointers, each to n elements on `device`.  For every
+ *   lookup j, d_permuted_inputs[j] and d_permuted_tables[j] take exactly the bytes that
+ *   fr_lookup_permute_device(d_inputs[j], d_tables[j], n, form, ..) writes (steps 1-3 above); the
+ *   lookups are independent of each other.  The number of kernel launches does not depend on count:
+ *   every column of the call is a grid row of one set of launches (104 kernels and two memsets; 105
+ *   with SV_LOOKUP_TABLES_SORTED), where `count` single calls are 202 each.
+ *   Tables: entries of d_tables may be equal pointers, and a table that several lookups name is
+ *   read, converted and sorted ONCE per call.  Tables are deduplicated by pointer value only:
+ *   distinct pointers are distinct tables, and two of them may overlap (tables are only read).
+ *   Inputs are only read too; one input pointer may appear in several lookups.
+ *   flags = SV_LOOKUP_TABLES_SORTED: every table of the call is already in ascending canonical
+ *   order in `form` -- what fr_sort_device writes; a fixed table is the same for every proof, so
+ *   it can be sorted once per circuit.  The call then sorts no table: one pass converts it and
+ *   checks T[i-1] <= T[i] on the device, equal neighbours being legal; a violation is SV_ERR_ARG
+ *   ("table not sorted").
+ *   Failure: a leader of lookup j whose value is not in its table is SV_ERR_ARG ("not in table");
+ *   out_missing_rows[j] (a host array of count entries, may be NULL) is the smallest such row of
+ *   A'_j, or UINT64_MAX for a lookup that is fine, and *out_failed (host, may be NULL) the smallest
+ *   failing j, or UINT64_MAX.  The outputs of the lookups that did not fail are still exact.
+ * Checked before any device work, in this order:
+ *   1. bad form; an unknown flag bit; a null array; a null entry; an entry not 16-byte aligned
+ *                                                                                      SV_ERR_ARG
+ *   2. count == 0 or n == 0                                                            SV_ERR_EMPTY
+ *   3. count > SV_LOOKUP_BATCH_MAX or n > 2^26                                         SV_ERR_LEN
+ *   4. an output overlapping an input, a table or another output            SV_ERR_ARG ("overlaps")
+ * Rule 1 looks at all `count` entries of the four arrays before rule 3 looks at `count`: the arrays
+ * must really hold `count` entries, also in a call that is then refused with SV_ERR_LEN.
+ * An element not below r, in any input or table, is found on the device and is SV_ERR_ARG ("not
+ * reduced"); it wins over the other two device errors, ALL outputs are then unspecified, nothing
+ * outside them is written, and the next call is exact.  "table not sorted" wins over "not in
+ * table"; out_missing_rows and out_failed are written only by a call that returns SV_OK or "not in
+ * table".  Points 1 and 2 of "Streams" apply (ordered after `stream`, synchronous, one read-back of
+ * the lookups' heads at the end); re-entrant from any number of threads.  Pooled scratch per row:
+ * 65 B per sorted column (every input, and every distinct table unless the flag is set: two
+ * canonical images and the per-block digit counts), 16 B per lookup (four u32 lists), 32 B per
+ * table with the flag set (one image); a failed allocation is SV_ERR_OOM with nothing launched.
+ * Not covered: several z columns per grand-product call; the blinding rows; host buffers;
+ * multi-device columns; a public batched sort.                                                 */
+#define SV_LOOKUP_BATCH_MAX 16 /* lookups per call (= SV_TERMS_LOOKUPS_MAX) */
+enum { SV_LOOKUP_TABLES_SORTED = 1 }; /* flags */
+int sv_bn254_fr_lookup_permute_batch_device(const sv_fe* const* d_inputs, const sv_fe* const* d_tables,
+                                            size_t count, size_t n, int form, uint32_t flags,
+                                            sv_fe* const* d_permuted_inputs,
+                                            sv_fe* const* d_permuted_tables,
+                                            uint64_t* out_missing_rows, uint64_t* out_failed,
+                                            int device, void* stream) SV_NOEXCEPT;
+
 /* ---- Poseidon sponge over BN254 Fr --------------------------
  * x^5 HADES permutation, width t = 3 (R_F 8, R_P 57, rate 2: the SDK's PoseidonTranscript,
  * snark-verifier-sdk/src/halo2.rs:52-71) or t = 5 (R_F 8, R_P 60, rate 4).  States are t

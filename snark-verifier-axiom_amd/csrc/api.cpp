@@ -23,6 +23,7 @@
 #include "host_poseidon.hpp"
 #include "kzg_open.hpp"
 #include "lookup_permute.hpp"
+#include "lp_batch_plan.hpp"
 #include "msm.hpp"
 #include "msm_batch.hpp"
 #include "msm_batch_plan.hpp"
@@ -2788,6 +2789,67 @@ int sv_bn254_fr_lookup_permute_device(const sv_fe* d_input, const sv_fe* d_table
   call.d_out = d_permuted_input;
   call.d_out_table = d_permuted_table;
   return lookup_permute_run(call, device, stream, out_missing_row);
+  SV_GUARD_END
+}
+
+int sv_bn254_fr_lookup_permute_batch_device(const sv_fe* const* d_inputs, const sv_fe* const* d_tables, size_t count,
+                                            size_t n, int form, uint32_t flags, sv_fe* const* d_permuted_inputs,
+                                            sv_fe* const* d_permuted_tables, uint64_t* out_missing_rows,
+                                            uint64_t* out_failed, int device, void* stream) noexcept {
+  SV_GUARD_BEGIN
+  // rules 1-4, the table slots and the scratch layout (csrc/lp_batch_plan.hpp)
+  const LpBatchPlan plan = lp_batch_plan(reinterpret_cast<const void* const*>(d_inputs),
+                                         reinterpret_cast<const void* const*>(d_tables), count, n, form, flags,
+                                         reinterpret_cast<void* const*>(d_permuted_inputs),
+                                         reinterpret_cast<void* const*>(d_permuted_tables));
+  if (plan.rule != kLpbOk) {
+    if (plan.rule == kLpbRuleArg && form != SV_CANONICAL && form != SV_MONTGOMERY) sv::set_error("bad form %d", form);
+    else if (plan.rule == kLpbRuleOverlap) sv::set_error("%s: overlaps", plan.why);
+    else sv::set_error("%s (count = %zu, n = %zu)", plan.why, count, n);
+    return plan.rule == kLpbRuleEmpty ? SV_ERR_EMPTY : plan.rule == kLpbRuleLen ? SV_ERR_LEN : SV_ERR_ARG;
+  }
+  if (resolve_gpus(0) == 0) return SV_ERR_DEVICE;
+  DrainedLease dl(device, caller_stream(stream));
+  if (!dl.lease.ok()) return SV_ERR_DEVICE;
+  Workspace* ws = dl.ws();
+  const size_t heads = count * kLpHeadBytes;
+  SV_TRY(ws->reserve(plan.total));
+  SV_TRY(ws->reserve_pinned(heads));
+  LpBatchCall call{};
+  call.plan = &plan;
+  call.d_inputs = d_inputs;
+  call.n = n;
+  call.form = form;
+  call.d_out_inputs = d_permuted_inputs;
+  call.d_out_tables = d_permuted_tables;
+  SV_TRY(lookup_permute_batch_enqueue(call, ws->buf, ws->stream));
+  SV_HIP(hipMemcpyAsync(ws->pinned, ws->buf + plan.heads, heads, hipMemcpyDeviceToHost, ws->stream));
+  SV_HIP(hipStreamSynchronize(ws->stream));
+  dl.armed = false;
+  uint32_t errv;
+  memcpy(&errv, ws->pinned + kLpErrOffset, sizeof errv);
+  if (errv & kLpErrNotReduced) {
+    sv::set_error("invalid input: element not reduced mod r");
+    return SV_ERR_ARG;
+  }
+  if (errv & kLpErrNotSorted) {
+    sv::set_error("table not sorted: SV_LOOKUP_TABLES_SORTED promises ascending canonical order");
+    return SV_ERR_ARG;
+  }
+  uint64_t failed = UINT64_MAX, failed_row = 0;
+  for (size_t j = count; j-- > 0;) {
+    uint64_t missing;
+    memcpy(&missing, ws->pinned + j * kLpHeadBytes + kLpMissingOffset, sizeof missing);
+    if (out_missing_rows) out_missing_rows[j] = missing ? UINT64_MAX - missing : UINT64_MAX;
+    if (missing) failed = j, failed_row = UINT64_MAX - missing;
+  }
+  if (out_failed) *out_failed = failed;
+  if (failed != UINT64_MAX) {
+    sv::set_error("lookup %llu: row %llu of the permuted input holds a value that is not in table",
+                  (unsigned long long)failed, (unsigned long long)failed_row);
+    return SV_ERR_ARG;
+  }
+  return SV_OK;
   SV_GUARD_END
 }
 

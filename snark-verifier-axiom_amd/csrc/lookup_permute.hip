@@ -38,6 +38,18 @@
 //   k_lp_write    S'[i] = A'[i] at a leader, and for k < m S'[rep_row[k]] = T[un_pos[m - 1 - k]]: the
 //                 smallest leftover goes to the last repeated row, as halo2's pop() does.
 // Comparisons are on the canonical images; the outputs are converted to `form` where they are written.
+//
+// Every kernel's work is a __device__ body (lp_*) with two entry kernels around it.  k_lp_* are the
+// single calls' entries, with the pointers of their one column as kernel parameters: a sort is 99
+// launches, a permutation 202, its two sorts one after the other.  k_lpb_* are the batch call's
+// entries with a column dimension, blockIdx.y: a call's columns are its lookups' inputs and, after
+// them, its distinct tables (csrc/lp_batch_plan.hpp names them); each sorted column has its own state,
+// image pair and per-block counts, and each lookup its own head, flag and list arrays, totals and
+// carries, and an entry finds its column's pointers in the by-value LpGeom.  One set of launches
+// serves every column: the blocks of a column for which a pass is dead return at their first
+// instruction while the other columns' blocks run: 104 kernels whatever the number of lookups.  A table
+// the caller has sorted skips the radix sort: k_lpb_table converts it into its one image and checks
+// T[i - 1] <= T[i] (one more launch, 105).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +57,7 @@
 
 #include "field.hpp"
 #include "lookup_permute.hpp"
+#include "lp_batch_plan.hpp"
 #include "runtime.hpp"
 
 namespace sv {
@@ -74,8 +87,10 @@ struct LpHead {
   uint32_t err, pad0;
   unsigned long long missing;  // UINT64_MAX - row, 0 = none
   uint32_t repeats, pad1;      // m
+  uint32_t pad2[10];           // a batch has one head per lookup, kLpHeadBytes apart
 };
-static_assert(sizeof(LpHead) <= kLpHeadBytes && offsetof(LpHead, missing) == kLpMissingOffset, "head layout");
+static_assert(sizeof(LpHead) == kLpHeadBytes && offsetof(LpHead, missing) == kLpMissingOffset, "head layout");
+constexpr uint32_t kErrNotReduced = kLpErrNotReduced, kErrNotSorted = kLpErrNotSorted;  // bits of heads[0].err
 
 __device__ __forceinline__ Fr ld_fr(const uint4* q) {
   const uint4 a = q[0], b = q[1];
@@ -120,9 +135,11 @@ __device__ __forceinline__ void block_exscan2(uint32_t* sm, uint32_t& a, uint32_
   __syncthreads();
 }
 
+// ---- the bodies ------------------------------------------------------------------------------------
+
 template <bool kMont>
-__global__ void __launch_bounds__(kNT) k_lp_first(const uint4* __restrict__ in, uint4* __restrict__ image, uint32_t n,
-                                                  uint32_t nb, LpState* __restrict__ state, LpHead* __restrict__ head) {
+__device__ __forceinline__ void lp_first(const uint4* __restrict__ in, uint4* __restrict__ image, uint32_t n, uint32_t nb,
+                                         LpState* __restrict__ state, LpHead* __restrict__ head) {
   __shared__ uint32_t h[kLpDigits * 256];
   const int t = (int)threadIdx.x;
   for (int e = t; e < (int)kLpDigits * 256; e += kNT) h[e] = 0;
@@ -146,10 +163,39 @@ __global__ void __launch_bounds__(kNT) k_lp_first(const uint4* __restrict__ in, 
   uint32_t* g = &state->hist[0][0];
   for (int e = t; e < (int)kLpDigits * 256; e += kNT)
     if (h[e]) atomicAdd(g + e, h[e]);
-  if (bad) atomicOr(&head->err, 1u);
+  if (bad) atomicOr(&head->err, kErrNotReduced);
 }
 
-__global__ void __launch_bounds__(kNT) k_lp_plan(LpState* __restrict__ state) {
+// A table the caller has sorted: the one pass that reads it.  The canonical image is written, every
+// element is tested below r, and element i is compared with element i - 1 (read and converted again:
+// a tile's first element has its predecessor in another block).
+template <bool kMont>
+__device__ __forceinline__ void lp_table(const uint4* __restrict__ in, uint4* __restrict__ image, uint32_t n, uint32_t nb,
+                                         LpHead* __restrict__ head) {
+  const int t = (int)threadIdx.x;
+  bool bad = false, unsorted = false;
+  for (uint32_t tile = blockIdx.x; tile < nb; tile += gridDim.x) {
+#pragma unroll 1
+    for (int j = 0; j < kPer; j++) {
+      const uint32_t i = tile * kLpTile + (uint32_t)(j * kNT + t);
+      if (i < n) {
+        Fr a = ld_fr(in + 2 * (size_t)i);
+        bad |= !a.is_reduced();
+        if (kMont) a = fe_from_mont(a);
+        st_fr(image + 2 * (size_t)i, a);
+        if (i > 0) {
+          Fr b = ld_fr(in + 2 * (size_t)(i - 1));
+          if (kMont) b = fe_from_mont(b);
+          unsorted |= key_less(a, b);
+        }
+      }
+    }
+  }
+  if (bad) atomicOr(&head->err, kErrNotReduced);
+  if (unsorted) atomicOr(&head->err, kErrNotSorted);
+}
+
+__device__ __forceinline__ void lp_plan(LpState* __restrict__ state) {
   __shared__ uint32_t sm[4 * kNT];
   const int t = (int)threadIdx.x;
   uint32_t image = 0;
@@ -164,9 +210,8 @@ __global__ void __launch_bounds__(kNT) k_lp_plan(LpState* __restrict__ state) {
   if (t == 0) state->final_image = image;
 }
 
-__global__ void __launch_bounds__(kNT) k_lp_count(const LpState* __restrict__ state, uint32_t pass,
-                                                  const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1,
-                                                  uint32_t n, uint32_t* __restrict__ counts) {
+__device__ __forceinline__ void lp_count(const LpState* __restrict__ state, uint32_t pass, const uint32_t* __restrict__ img0,
+                                         const uint32_t* __restrict__ img1, uint32_t n, uint32_t* __restrict__ counts) {
   const uint32_t pw = state->plan[pass];
   if (!(pw & 1u)) return;
   __shared__ uint32_t h[256];
@@ -185,8 +230,8 @@ __global__ void __launch_bounds__(kNT) k_lp_count(const LpState* __restrict__ st
 
 // Block d: the counts of digit d over the nb blocks, c = ceil(nb / kNT) consecutive ones per thread,
 // become the positions at which the blocks' keys of that digit start.
-__global__ void __launch_bounds__(kNT) k_lp_offsets(const LpState* __restrict__ state, uint32_t pass, uint32_t nb,
-                                                    uint32_t* __restrict__ counts) {
+__device__ __forceinline__ void lp_offsets(const LpState* __restrict__ state, uint32_t pass, uint32_t nb,
+                                           uint32_t* __restrict__ counts) {
   if (!(state->plan[pass] & 1u)) return;
   __shared__ uint32_t sm[4 * kNT];
   const int t = (int)threadIdx.x;
@@ -206,9 +251,8 @@ __global__ void __launch_bounds__(kNT) k_lp_offsets(const LpState* __restrict__ 
     }
 }
 
-__global__ void __launch_bounds__(kNT) k_lp_scatter(const LpState* __restrict__ state, uint32_t pass,
-                                                    uint4* __restrict__ img0, uint4* __restrict__ img1, uint32_t n,
-                                                    const uint32_t* __restrict__ offsets) {
+__device__ __forceinline__ void lp_scatter(const LpState* __restrict__ state, uint32_t pass, uint4* __restrict__ img0,
+                                           uint4* __restrict__ img1, uint32_t n, const uint32_t* __restrict__ offsets) {
   const uint32_t pw = state->plan[pass];
   if (!(pw & 1u)) return;
   __shared__ uint32_t cnt[kRuns * 256];
@@ -259,27 +303,18 @@ __device__ __forceinline__ const uint4* final_image(const LpState* state, const 
   return state->final_image ? img1 : img0;
 }
 
+// src: the image that holds the sorted keys
 template <bool kMont>
-__global__ void __launch_bounds__(kNT) k_lp_finish(const LpState* __restrict__ state, const uint4* __restrict__ img0,
-                                                   const uint4* __restrict__ img1, uint32_t n, uint4* __restrict__ out) {
-  const uint4* src = final_image(state, img0, img1);
+__device__ __forceinline__ void lp_finish(const uint4* __restrict__ src, uint32_t n, uint4* __restrict__ out) {
   const uint32_t i = blockIdx.x * kNT + threadIdx.x;
   if (i >= n) return;
   const Fr a = ld_fr(src + 2 * (size_t)i);
   st_fr(out + 2 * (size_t)i, kMont ? fe_to_mont(a) : a);
 }
 
-// The images of the permutation: A' = the final image of pair a, T = that of pair s.
-struct LpImages {
-  const LpState* sa;
-  const LpState* ss;
-  const uint4 *a0, *a1, *s0, *s1;
-};
-
-__global__ void __launch_bounds__(kNT) k_lp_leaders(const LpImages im, uint32_t n, uint32_t* __restrict__ repeat,
-                                                    uint32_t* __restrict__ used, LpHead* __restrict__ head) {
-  const uint4* A = final_image(im.sa, im.a0, im.a1);
-  const uint4* T = final_image(im.ss, im.s0, im.s1);
+// A = the sorted input, T = the sorted table
+__device__ __forceinline__ void lp_leaders(const uint4* A, const uint4* T, uint32_t n, uint32_t* __restrict__ repeat,
+                                           uint32_t* __restrict__ used, LpHead* __restrict__ head) {
   const uint32_t i = blockIdx.x * kNT + threadIdx.x;
   if (i >= n) return;
   const Fr a = ld_fr(A + 2 * (size_t)i);
@@ -308,8 +343,8 @@ __device__ __forceinline__ void load_flags(const uint32_t* repeat, const uint32_
   }
 }
 
-__global__ void __launch_bounds__(kNT) k_lp_totals(const uint32_t* __restrict__ repeat, const uint32_t* __restrict__ used,
-                                                   uint32_t n, uint32_t* __restrict__ totals) {
+__device__ __forceinline__ void lp_totals(const uint32_t* __restrict__ repeat, const uint32_t* __restrict__ used, uint32_t n,
+                                          uint32_t* __restrict__ totals) {
   __shared__ uint32_t sm[4 * kNT];
   uint32_t r[kPer], u[kPer], a = 0, b = 0, ta, tb;
   load_flags(repeat, used, n, r, u);
@@ -320,8 +355,8 @@ __global__ void __launch_bounds__(kNT) k_lp_totals(const uint32_t* __restrict__ 
 }
 
 // One block over the nb pairs of block totals, c = ceil(nb / kNT) consecutive pairs per thread.
-__global__ void __launch_bounds__(kNT) k_lp_carries(const uint32_t* __restrict__ totals, uint32_t nb,
-                                                    uint32_t* __restrict__ carries, LpHead* __restrict__ head) {
+__device__ __forceinline__ void lp_carries(const uint32_t* __restrict__ totals, uint32_t nb, uint32_t* __restrict__ carries,
+                                           LpHead* __restrict__ head) {
   __shared__ uint32_t sm[4 * kNT];
   const int t = (int)threadIdx.x;
   const uint32_t c = (nb + kNT - 1) / kNT;
@@ -338,9 +373,9 @@ __global__ void __launch_bounds__(kNT) k_lp_carries(const uint32_t* __restrict__
   if (t == 0) head->repeats = ta;
 }
 
-__global__ void __launch_bounds__(kNT) k_lp_lists(const uint32_t* __restrict__ repeat, const uint32_t* __restrict__ used,
-                                                  uint32_t n, const uint32_t* __restrict__ carries,
-                                                  uint32_t* __restrict__ rep_row, uint32_t* __restrict__ un_pos) {
+__device__ __forceinline__ void lp_lists(const uint32_t* __restrict__ repeat, const uint32_t* __restrict__ used, uint32_t n,
+                                         const uint32_t* __restrict__ carries, uint32_t* __restrict__ rep_row,
+                                         uint32_t* __restrict__ un_pos) {
   __shared__ uint32_t sm[4 * kNT];
   uint32_t r[kPer], u[kPer], a = 0, b = 0, ta, tb;
   load_flags(repeat, used, n, r, u);
@@ -357,22 +392,187 @@ __global__ void __launch_bounds__(kNT) k_lp_lists(const uint32_t* __restrict__ r
 }
 
 template <bool kMont>
-__global__ void __launch_bounds__(kNT) k_lp_write(const LpImages im, uint32_t n, const uint32_t* __restrict__ repeat,
-                                                  const uint32_t* __restrict__ rep_row, const uint32_t* __restrict__ un_pos,
-                                                  const LpHead* __restrict__ head, uint4* __restrict__ out) {
-  const uint4* A = final_image(im.sa, im.a0, im.a1);
-  const uint4* T = final_image(im.ss, im.s0, im.s1);
+__device__ __forceinline__ void lp_write(const uint4* A, const uint4* T, uint32_t n, const uint32_t* __restrict__ repeat,
+                                         const uint32_t* __restrict__ rep_row, const uint32_t* __restrict__ un_pos,
+                                         const LpHead* __restrict__ head, uint4* __restrict__ out) {
   const uint32_t i = blockIdx.x * kNT + threadIdx.x;
   if (i >= n) return;
   if (!repeat[i]) {
     const Fr a = ld_fr(A + 2 * (size_t)i);
     st_fr(out + 2 * (size_t)i, kMont ? fe_to_mont(a) : a);
   }
-  const uint32_t m = head->repeats;  // a failed call has more unused positions than repeats: still in range
+  const uint32_t m = head->repeats;  // a failed lookup has more unused positions than repeats: still in range
   if (i < m) {
     const Fr l = ld_fr(T + 2 * (size_t)un_pos[m - 1 - i]);
     st_fr(out + 2 * (size_t)rep_row[i], kMont ? fe_to_mont(l) : l);
   }
+}
+
+// ---- the single calls' entries: one column, its pointers as kernel parameters ---------------------
+
+template <bool kMont>
+__global__ void __launch_bounds__(kNT) k_lp_first(const uint4* __restrict__ in, uint4* __restrict__ image, uint32_t n,
+                                                  uint32_t nb, LpState* __restrict__ state, LpHead* __restrict__ head) {
+  lp_first<kMont>(in, image, n, nb, state, head);
+}
+
+__global__ void __launch_bounds__(kNT) k_lp_plan(LpState* __restrict__ state) { lp_plan(state); }
+
+__global__ void __launch_bounds__(kNT) k_lp_count(const LpState* __restrict__ state, uint32_t pass,
+                                                  const uint32_t* __restrict__ img0, const uint32_t* __restrict__ img1,
+                                                  uint32_t n, uint32_t* __restrict__ counts) {
+  lp_count(state, pass, img0, img1, n, counts);
+}
+
+__global__ void __launch_bounds__(kNT) k_lp_offsets(const LpState* __restrict__ state, uint32_t pass, uint32_t nb,
+                                                    uint32_t* __restrict__ counts) {
+  lp_offsets(state, pass, nb, counts);
+}
+
+__global__ void __launch_bounds__(kNT) k_lp_scatter(const LpState* __restrict__ state, uint32_t pass,
+                                                    uint4* __restrict__ img0, uint4* __restrict__ img1, uint32_t n,
+                                                    const uint32_t* __restrict__ offsets) {
+  lp_scatter(state, pass, img0, img1, n, offsets);
+}
+
+template <bool kMont>
+__global__ void __launch_bounds__(kNT) k_lp_finish(const LpState* __restrict__ state, const uint4* __restrict__ img0,
+                                                   const uint4* __restrict__ img1, uint32_t n, uint4* __restrict__ out) {
+  lp_finish<kMont>(final_image(state, img0, img1), n, out);
+}
+
+// The images of the permutation: A' = the final image of pair a, T = that of pair s.
+struct LpImages {
+  const LpState* sa;
+  const LpState* ss;
+  const uint4 *a0, *a1, *s0, *s1;
+};
+
+__global__ void __launch_bounds__(kNT) k_lp_leaders(const LpImages im, uint32_t n, uint32_t* __restrict__ repeat,
+                                                    uint32_t* __restrict__ used, LpHead* __restrict__ head) {
+  lp_leaders(final_image(im.sa, im.a0, im.a1), final_image(im.ss, im.s0, im.s1), n, repeat, used, head);
+}
+
+__global__ void __launch_bounds__(kNT) k_lp_totals(const uint32_t* __restrict__ repeat, const uint32_t* __restrict__ used,
+                                                   uint32_t n, uint32_t* __restrict__ totals) {
+  lp_totals(repeat, used, n, totals);
+}
+
+__global__ void __launch_bounds__(kNT) k_lp_carries(const uint32_t* __restrict__ totals, uint32_t nb,
+                                                    uint32_t* __restrict__ carries, LpHead* __restrict__ head) {
+  lp_carries(totals, nb, carries, head);
+}
+
+__global__ void __launch_bounds__(kNT) k_lp_lists(const uint32_t* __restrict__ repeat, const uint32_t* __restrict__ used,
+                                                  uint32_t n, const uint32_t* __restrict__ carries,
+                                                  uint32_t* __restrict__ rep_row, uint32_t* __restrict__ un_pos) {
+  lp_lists(repeat, used, n, carries, rep_row, un_pos);
+}
+
+template <bool kMont>
+__global__ void __launch_bounds__(kNT) k_lp_write(const LpImages im, uint32_t n, const uint32_t* __restrict__ repeat,
+                                                  const uint32_t* __restrict__ rep_row, const uint32_t* __restrict__ un_pos,
+                                                  const LpHead* __restrict__ head, uint4* __restrict__ out) {
+  lp_write<kMont>(final_image(im.sa, im.a0, im.a1), final_image(im.ss, im.s0, im.s1), n, repeat, rep_row, un_pos, head, out);
+}
+
+// ---- the batch call's entries: a column dimension ------------------------------------------------
+
+// What every batch kernel is given by value.  A call has columns: the lookups' inputs are columns
+// [0, lookups), the tables come after them.  The first sorted_cols columns go through the radix sort
+// and have a state, a block of per-block counts and an image pair; a column past them is a table the
+// caller has sorted, with one image.  A sort launch covers the columns blockIdx.y; lookup j of the
+// permutation's kernels is blockIdx.y.  The per-lookup arrays are strided by lookup.
+struct LpGeom {
+  LpHead* heads;     // lookup j: heads[j]; heads[0].err is the whole call's
+  LpState* states;   // column c < sorted_cols
+  uint4* images;     // column c < sorted_cols: images 2c, 2c + 1; past them one each
+  uint32_t* counts;  // column c < sorted_cols
+  uint32_t *repeat, *used, *rep_row, *un_pos, *totals, *carries;
+  size_t image_stride, counts_stride, flag_stride, tot_stride;  // in uint4, u32, u32, u32
+  uint32_t n, nb;
+  uint32_t sorted_cols;
+  uint8_t table_col[kLpbMax];  // the column of lookup j's table
+};
+struct LpIn {
+  const uint4* p[2 * kLpbMax];  // by column of the launch
+};
+struct LpOut {
+  uint4* p[kLpbMax];
+};
+
+__device__ __forceinline__ uint4* image_of(const LpGeom& g, uint32_t c, uint32_t parity) {
+  const size_t k = c < g.sorted_cols ? 2 * (size_t)c + parity : 2 * (size_t)g.sorted_cols + (c - g.sorted_cols);
+  return g.images + k * g.image_stride;
+}
+// the image that holds column c's sorted keys
+__device__ __forceinline__ const uint4* sorted_image(const LpGeom& g, uint32_t c) {
+  return image_of(g, c, c < g.sorted_cols ? g.states[c].final_image : 0u);
+}
+
+template <bool kMont>
+__global__ void __launch_bounds__(kNT) k_lpb_first(const LpIn ins, const LpGeom g) {
+  const uint32_t c = blockIdx.y;
+  lp_first<kMont>(ins.p[c], image_of(g, c, 0), g.n, g.nb, g.states + c, g.heads);
+}
+
+// the table slots: columns col0 + blockIdx.y, past the sorted ones
+template <bool kMont>
+__global__ void __launch_bounds__(kNT) k_lpb_table(const LpIn tabs, const LpGeom g, uint32_t col0) {
+  lp_table<kMont>(tabs.p[blockIdx.y], image_of(g, col0 + blockIdx.y, 0), g.n, g.nb, g.heads);
+}
+
+__global__ void __launch_bounds__(kNT) k_lpb_plan(const LpGeom g) { lp_plan(g.states + blockIdx.y); }
+
+__global__ void __launch_bounds__(kNT) k_lpb_count(const LpGeom g, uint32_t pass) {
+  const uint32_t c = blockIdx.y;
+  lp_count(g.states + c, pass, reinterpret_cast<const uint32_t*>(image_of(g, c, 0)),
+           reinterpret_cast<const uint32_t*>(image_of(g, c, 1)), g.n, g.counts + c * g.counts_stride);
+}
+
+__global__ void __launch_bounds__(kNT) k_lpb_offsets(const LpGeom g, uint32_t pass) {
+  const uint32_t c = blockIdx.y;
+  lp_offsets(g.states + c, pass, g.nb, g.counts + c * g.counts_stride);
+}
+
+__global__ void __launch_bounds__(kNT) k_lpb_scatter(const LpGeom g, uint32_t pass) {
+  const uint32_t c = blockIdx.y;
+  lp_scatter(g.states + c, pass, image_of(g, c, 0), image_of(g, c, 1), g.n, g.counts + c * g.counts_stride);
+}
+
+template <bool kMont>
+__global__ void __launch_bounds__(kNT) k_lpb_finish(const LpOut outs, const LpGeom g) {
+  lp_finish<kMont>(sorted_image(g, blockIdx.y), g.n, outs.p[blockIdx.y]);
+}
+
+// Lookup j = blockIdx.y reads A' = the sorted image of column j and T = that of column table_col[j].
+__global__ void __launch_bounds__(kNT) k_lpb_leaders(const LpGeom g) {
+  const uint32_t j = blockIdx.y;
+  lp_leaders(sorted_image(g, j), sorted_image(g, g.table_col[j]), g.n, g.repeat + j * g.flag_stride,
+             g.used + j * g.flag_stride, g.heads + j);
+}
+
+__global__ void __launch_bounds__(kNT) k_lpb_totals(const LpGeom g) {
+  const uint32_t j = blockIdx.y;
+  lp_totals(g.repeat + j * g.flag_stride, g.used + j * g.flag_stride, g.n, g.totals + j * g.tot_stride);
+}
+
+__global__ void __launch_bounds__(kNT) k_lpb_carries(const LpGeom g) {
+  const uint32_t j = blockIdx.y;
+  lp_carries(g.totals + j * g.tot_stride, g.nb, g.carries + j * g.tot_stride, g.heads + j);
+}
+
+__global__ void __launch_bounds__(kNT) k_lpb_lists(const LpGeom g) {
+  const uint32_t j = blockIdx.y;
+  lp_lists(g.repeat + j * g.flag_stride, g.used + j * g.flag_stride, g.n, g.carries + j * g.tot_stride,
+           g.rep_row + j * g.flag_stride, g.un_pos + j * g.flag_stride);
+}
+
+template <bool kMont>
+__global__ void __launch_bounds__(kNT) k_lpb_write(const LpOut outs, const LpGeom g) {
+  const uint32_t j = blockIdx.y;
+  lp_write<kMont>(sorted_image(g, j), sorted_image(g, g.table_col[j]), g.n, g.repeat + j * g.flag_stride,
+                  g.rep_row + j * g.flag_stride, g.un_pos + j * g.flag_stride, g.heads + j, outs.p[j]);
 }
 
 constexpr size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
@@ -424,6 +624,11 @@ void enqueue_finish(bool mont, uint32_t n, const LpState* state, const uint4* im
   else hipLaunchKernelGGL(k_lp_finish<false>, dim3(rows), dim3(kNT), 0, st, state, img0, img1, n, out);
 }
 
+template <class T>
+T* at(void* scratch, size_t offset) {
+  return reinterpret_cast<T*>(static_cast<char*>(scratch) + offset);
+}
+
 }  // namespace
 
 size_t lookup_permute_scratch_bytes(size_t n, bool permute) { return layout(n, permute).total; }
@@ -468,6 +673,82 @@ int lookup_permute_enqueue(const LpCall& call, void* d_scratch, hipStream_t st) 
     if (mont) hipLaunchKernelGGL(k_lp_write<true>, dim3(rows), dim3(kNT), 0, st, im, n, repeat, rep_row, un_pos, head, out);
     else hipLaunchKernelGGL(k_lp_write<false>, dim3(rows), dim3(kNT), 0, st, im, n, repeat, rep_row, un_pos, head, out);
   }
+  SV_HIP(hipGetLastError());
+  return SV_OK;
+}
+
+// Every column of the batch in one set of launches: 104 kernels (105 with tables the caller has
+// sorted) and two memsets, whatever the number of lookups.
+int lookup_permute_batch_enqueue(const LpBatchCall& call, void* d_scratch, hipStream_t st) {
+  static_assert(sizeof(LpState) == kLpbStateBytes && kLpHeadBytes == kLpbHeadBytes && kLpTile == kLpbTile &&
+                    kLpMaxRows == kLpbMaxRows && sizeof(sv_fe) == kLpbElem,
+                "lp_batch_plan.hpp lays out this file's scratch");
+  static_assert(kLpbMax == SV_LOOKUP_BATCH_MAX && kLpbTablesSorted == SV_LOOKUP_TABLES_SORTED &&
+                    kLpbCanonical == SV_CANONICAL && kLpbMontgomery == SV_MONTGOMERY,
+                "lp_batch_plan.hpp's numbers are the header's");
+  const LpBatchPlan& p = *call.plan;
+  if (p.rule != kLpbOk || p.count == 0 || p.count > kLpbMax || p.slots == 0 || p.slots > p.count || call.n == 0 ||
+      call.n > kLpMaxRows) {
+    set_error("lookup permute batch: not a plan of an accepted call");
+    return SV_ERR_ARG;
+  }
+  const bool mont = call.form == SV_MONTGOMERY;
+  const bool presorted = p.sorted_cols == p.count;
+  LpGeom g{};
+  g.n = (uint32_t)call.n;
+  g.nb = (g.n + kLpTile - 1) / kLpTile;
+  g.sorted_cols = p.sorted_cols;
+  g.heads = at<LpHead>(d_scratch, p.heads);
+  g.states = at<LpState>(d_scratch, p.states);
+  g.counts = at<uint32_t>(d_scratch, p.counts);
+  g.images = at<uint4>(d_scratch, p.images);
+  g.repeat = at<uint32_t>(d_scratch, p.repeat);
+  g.used = at<uint32_t>(d_scratch, p.used);
+  g.rep_row = at<uint32_t>(d_scratch, p.rep_row);
+  g.un_pos = at<uint32_t>(d_scratch, p.un_pos);
+  g.totals = at<uint32_t>(d_scratch, p.totals);
+  g.carries = at<uint32_t>(d_scratch, p.carries);
+  g.image_stride = p.image_stride / sizeof(uint4);
+  g.counts_stride = p.counts_stride / sizeof(uint32_t);
+  g.flag_stride = p.flag_stride / sizeof(uint32_t);
+  g.tot_stride = p.tot_stride / sizeof(uint32_t);
+  LpIn ins{}, tabs{};
+  LpOut out_a{}, out_s{};
+  for (uint32_t j = 0; j < p.count; j++) {
+    ins.p[j] = reinterpret_cast<const uint4*>(call.d_inputs[j]);
+    out_a.p[j] = reinterpret_cast<uint4*>(call.d_out_inputs[j]);
+    out_s.p[j] = reinterpret_cast<uint4*>(call.d_out_tables[j]);
+    g.table_col[j] = (uint8_t)(p.count + p.slot[j]);
+  }
+  for (uint32_t s = 0; s < p.slots; s++) {
+    tabs.p[s] = reinterpret_cast<const uint4*>(p.table[s]);
+    if (!presorted) ins.p[p.count + s] = tabs.p[s];
+  }
+  const uint32_t cols = p.sorted_cols, lookups = p.count;
+  const uint32_t first = std::min(g.nb, kFirstBlocksMax), rows = (g.n + kNT - 1) / kNT;
+  // the heads and the histograms start at zero, and every lookup's used flags
+  SV_HIP(hipMemsetAsync(d_scratch, 0, p.zeroed, st));
+  SV_HIP(hipMemsetAsync(g.used, 0, p.count * p.flag_stride, st));
+  if (presorted) {
+    if (mont) hipLaunchKernelGGL(k_lpb_table<true>, dim3(first, p.slots), dim3(kNT), 0, st, tabs, g, p.count);
+    else hipLaunchKernelGGL(k_lpb_table<false>, dim3(first, p.slots), dim3(kNT), 0, st, tabs, g, p.count);
+  }
+  if (mont) hipLaunchKernelGGL(k_lpb_first<true>, dim3(first, cols), dim3(kNT), 0, st, ins, g);
+  else hipLaunchKernelGGL(k_lpb_first<false>, dim3(first, cols), dim3(kNT), 0, st, ins, g);
+  hipLaunchKernelGGL(k_lpb_plan, dim3(1, cols), dim3(kNT), 0, st, g);
+  for (uint32_t pass = 0; pass < kLpDigits; pass++) {
+    hipLaunchKernelGGL(k_lpb_count, dim3(g.nb, cols), dim3(kNT), 0, st, g, pass);
+    hipLaunchKernelGGL(k_lpb_offsets, dim3(256, cols), dim3(kNT), 0, st, g, pass);
+    hipLaunchKernelGGL(k_lpb_scatter, dim3(g.nb, cols), dim3(kNT), 0, st, g, pass);
+  }
+  if (mont) hipLaunchKernelGGL(k_lpb_finish<true>, dim3(rows, lookups), dim3(kNT), 0, st, out_a, g);
+  else hipLaunchKernelGGL(k_lpb_finish<false>, dim3(rows, lookups), dim3(kNT), 0, st, out_a, g);
+  hipLaunchKernelGGL(k_lpb_leaders, dim3(rows, lookups), dim3(kNT), 0, st, g);
+  hipLaunchKernelGGL(k_lpb_totals, dim3(g.nb, lookups), dim3(kNT), 0, st, g);
+  hipLaunchKernelGGL(k_lpb_carries, dim3(1, lookups), dim3(kNT), 0, st, g);
+  hipLaunchKernelGGL(k_lpb_lists, dim3(g.nb, lookups), dim3(kNT), 0, st, g);
+  if (mont) hipLaunchKernelGGL(k_lpb_write<true>, dim3(rows, lookups), dim3(kNT), 0, st, out_s, g);
+  else hipLaunchKernelGGL(k_lpb_write<false>, dim3(rows, lookups), dim3(kNT), 0, st, out_s, g);
   SV_HIP(hipGetLastError());
   return SV_OK;
 }

@@ -42,10 +42,34 @@ struct LpCall {
 // the repeated rows, the unused table positions) and the scans' block totals and carries.  Per row:
 // 65 B (sort), 145 B (permute).
 constexpr size_t kLpErrOffset = 0, kLpMissingOffset = 8, kLpHeadBytes = 64;
+constexpr uint32_t kLpErrNotReduced = 1, kLpErrNotSorted = 2;  // bits of the error flag
 size_t lookup_permute_scratch_bytes(size_t n, bool permute);
 
 // Enqueues the launches on `st`.  Nothing is synchronised: the caller reads the first kLpHeadBytes
 // of d_scratch (layout above) after the stream has drained.
 int lookup_permute_enqueue(const LpCall& call, void* d_scratch, hipStream_t st);
+
+// A batch of lookups over n rows each (sv_bn254_fr_lookup_permute_batch_device), past the checks of
+// lp_batch_plan.hpp: `plan` is that call's accepted plan and names the distinct tables; the three
+// arrays are host arrays of plan->count device pointers.  The scratch is plan->total bytes, laid out
+// by the plan: one head of kLpHeadBytes per lookup from offset 0 (lookup j's missing row at j *
+// kLpHeadBytes + kLpMissingOffset; the error flag of the whole call is head 0's), then per sorted
+// column -- every input, and every distinct table unless the caller has sorted them -- a state, the
+// per-block digit counts and two canonical images (65 B per row), one image per table the caller
+// has sorted (32 B per row), and four u32 per row and lookup (16 B) with their block totals and
+// carries.
+struct LpBatchPlan;
+struct LpBatchCall {
+  const LpBatchPlan* plan;
+  const sv_fe* const* d_inputs;
+  size_t n;
+  int form;
+  sv_fe* const* d_out_inputs;
+  sv_fe* const* d_out_tables;
+};
+
+// Enqueues the launches on `st`, their number independent of the number of lookups.  Nothing is
+// synchronised: the caller reads the first plan->count heads after the stream has drained.
+int lookup_permute_batch_enqueue(const LpBatchCall& call, void* d_scratch, hipStream_t st);
 
 }  // namespace sv

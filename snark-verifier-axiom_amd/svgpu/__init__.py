@@ -222,5 +222,27 @@ def lookup_argument(inputs, tables, beta, gamma, z0=1, **kwargs):
     return permuted_input, permuted_table, z, total
 
 
+def lookup_permute_batch_device(inputs, tables, **kwargs):
+    """svgpu.device.lookup_permute_batch_device (imported on first use: that module needs torch)."""
+    from .device import lookup_permute_batch_device as run
+    return run(inputs, tables, **kwargs)
+
+
+def lookup_arguments(inputs, tables, beta, gamma, z0=1, **kwargs):
+    """The lookup arguments of a circuit on columns in HBM: one lookup_permute_batch_device over all
+    of them (`tables` a list, or one tensor that every lookup shares), then lookup_product per lookup
+    -> [(permuted_input, permuted_table, z, total), ..], per lookup what lookup_argument returns.
+    form= goes to every call, out= (pairs of tensors) and tables_sorted= to the permutation."""
+    out, tables_sorted = kwargs.pop("out", None), kwargs.pop("tables_sorted", False)
+    pairs = lookup_permute_batch_device(inputs, tables, out=out, tables_sorted=tables_sorted, **kwargs)
+    if not isinstance(tables, (list, tuple)):
+        tables = [tables] * len(pairs)
+    result = []
+    for a, s, (permuted_input, permuted_table) in zip(inputs, tables, pairs):
+        z, total = lookup_product(a, s, permuted_input, permuted_table, beta, gamma, z0=z0, **kwargs)
+        result.append((permuted_input, permuted_table, z, total))
+    return result
+
+
 def version() -> str:
     return lib.sv_version().decode()

@@ -28,6 +28,8 @@ SV_NTT_INVERSE = 1
 SV_EXT_LOG_MAX = 8         # log2 of the widest extension of coset_lde / quotient_coeffs
 SV_TERMS_COLUMNS_MAX = 64  # permutation columns (and z columns) per permutation_terms call
 SV_TERMS_LOOKUPS_MAX = 16  # lookups per lookup_terms call
+SV_LOOKUP_BATCH_MAX = 16   # lookups per lookup_permute_batch call
+SV_LOOKUP_TABLES_SORTED = 1  # lookup_permute_batch flag: every table is already sorted
 
 # opcodes of an expression program (sv_fr_expr_op.op)
 (SV_EXPR_COLUMN, SV_EXPR_CONST, SV_EXPR_NEG, SV_EXPR_ADD, SV_EXPR_SUB, SV_EXPR_RSUB, SV_EXPR_MUL, SV_EXPR_FOLD,
@@ -205,6 +207,9 @@ PROTOTYPES = [
     ("sv_bn254_fr_sort_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     ("sv_bn254_fr_lookup_permute_device", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
                                                    POINTER(c_uint64), c_int, c_void_p]),
+    ("sv_bn254_fr_lookup_permute_batch_device", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_int, c_uint32,
+                                                         c_void_p, c_void_p, POINTER(c_uint64), POINTER(c_uint64),
+                                                         c_int, c_void_p]),
     ("sv_bn254_poseidon_permute", c_int, [c_void_p, c_size_t, c_int, c_int]),
     ("sv_bn254_poseidon_permute_device", c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     ("sv_bn254_poseidon_squeeze", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

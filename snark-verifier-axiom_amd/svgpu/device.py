@@ -427,6 +427,65 @@ def lookup_permute_device(inputs: torch.Tensor, tables: torch.Tensor, form: int 
     return out[0], out[1]
 
 
+def lookup_permute_batch_device(inputs, tables, form: int = _lib.SV_MONTGOMERY, tables_sorted: bool = False, out=None):
+    """lookup_permute_device for the lookups of a circuit in one call whose launch count does not
+    depend on their number: `inputs` is a list of (n, 4) int64 tensors on one device, `tables` a list
+    of the same length or one tensor that every lookup shares -> [(permuted_input, permuted_table),
+    ..] in `form`, each pair what lookup_permute_device returns for that lookup.  Tables that are one
+    tensor (the same data_ptr) are sorted once.  tables_sorted=True promises that every table is
+    already ascending (what sort_device returns) and sorts none; a table that is not raises
+    ArgumentError ("table not sorted").  out=None allocates; out=[(a', s'), ..] are n-row tensors that
+    overlap nothing else of the call.  A value that is not in its table raises ArgumentError ("not in
+    table") with .lookup = the first failing lookup and .rows = per lookup the smallest such row of
+    its permuted input, None where the lookup is fine; the other lookups' outputs are then exact."""
+    if isinstance(tables, torch.Tensor):
+        tables = [tables] * len(inputs)
+    inputs, tables = list(inputs), list(tables)
+    if len(tables) != len(inputs):
+        raise _lib.LengthError(f"lookup_permute_batch: {len(tables)} tables for {len(inputs)} inputs")
+    if not inputs:
+        raise _lib.EmptyError("lookup_permute_batch: the batch should not be empty")
+    if len(inputs) > _lib.SV_LOOKUP_BATCH_MAX:
+        raise _lib.LengthError(f"lookup_permute_batch: {len(inputs)} lookups exceed SV_LOOKUP_BATCH_MAX = "
+                               f"{_lib.SV_LOOKUP_BATCH_MAX}")
+    for j, (a, s) in enumerate(zip(inputs, tables)):
+        _fr_column(a, f"lookup_permute_batch: inputs[{j}]")
+        _fr_column(s, f"lookup_permute_batch: tables[{j}]")
+    d = _dev_index(inputs[0])
+    dev, shape = inputs[0].device, inputs[0].shape
+    for t in inputs + tables:
+        if t.device != dev:
+            raise _lib.ArgumentError("lookup_permute_batch: the columns of a call live on one device")
+        if t.shape != shape:
+            raise _lib.LengthError(f"lookup_permute_batch: a column has {t.shape[0]} rows, inputs[0] {shape[0]}")
+    if out is None:
+        out = [(torch.empty_like(inputs[0]), torch.empty_like(inputs[0])) for _ in inputs]
+    out = [tuple(pair) for pair in out]
+    if len(out) != len(inputs) or any(len(pair) != 2 for pair in out):
+        raise _lib.LengthError(f"lookup_permute_batch: out is {len(inputs)} pairs of tensors")
+    for pair in out:
+        for o in pair:
+            if (not isinstance(o, torch.Tensor) or o.device != dev or o.dtype != torch.int64 or not o.is_contiguous()
+                    or o.shape != shape):
+                raise _lib.LengthError(f"lookup_permute_batch: out is pairs of contiguous {tuple(shape)} int64 tensors "
+                                       f"on {dev}")
+    count = len(inputs)
+    ptrs = ctypes.c_void_p * count
+    rows, failed = (ctypes.c_uint64 * count)(), ctypes.c_uint64(0)
+    rc = _lib.lib.sv_bn254_fr_lookup_permute_batch_device(
+        ptrs(*[t.data_ptr() for t in inputs]), ptrs(*[t.data_ptr() for t in tables]), count, shape[0], form,
+        _lib.SV_LOOKUP_TABLES_SORTED if tables_sorted else 0, ptrs(*[p[0].data_ptr() for p in out]),
+        ptrs(*[p[1].data_ptr() for p in out]), rows, ctypes.byref(failed), d, _stream_handle(dev))
+    try:
+        _lib.check(rc, "sv_bn254_fr_lookup_permute_batch_device")
+    except _lib.ArgumentError as e:
+        if "not in table" in str(e):
+            e.lookup = failed.value
+            e.rows = [None if r == 2**64 - 1 else r for r in rows]
+        raise
+    return out
+
+
 def _terms_column(t: torch.Tensor, n: int, dev, who: str, what: str) -> torch.Tensor:
     """_column for the terms calls: an (N, 4) int64 tensor on the call's device, made contiguous."""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 4:

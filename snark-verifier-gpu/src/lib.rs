@@ -98,6 +98,10 @@ pub const SV_EXT_LOG_MAX: u32 = 8;
 pub const SV_TERMS_COLUMNS_MAX: usize = 64;
 /// Lookups per sv_bn254_fr_lookup_terms_device call.
 pub const SV_TERMS_LOOKUPS_MAX: usize = 16;
+/// Lookups per `sv_bn254_fr_lookup_permute_batch_device` call.
+pub const SV_LOOKUP_BATCH_MAX: usize = 16;
+/// Flag of `sv_bn254_fr_lookup_permute_batch_device`: every table is already in ascending canonical order.
+pub const SV_LOOKUP_TABLES_SORTED: u32 = 1;
 /// sv_fr_lookup: the five extended columns of one lookup (z, a', s', A, S), all in HBM.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -309,6 +313,15 @@ extern "C" {
                                              d_permuted_input: *mut SvFe, d_permuted_table: *mut SvFe,
                                              out_missing_row: *mut u64, device: c_int,
                                              stream: *mut c_void) -> c_int;
+    /// `count` lookups in one call whose launch count does not depend on `count`: the four arrays are host
+    /// arrays of device pointers; equal table pointers are one table, sorted once; out_missing_rows (count
+    /// entries) and out_failed are host pointers and may be null.
+    pub fn sv_bn254_fr_lookup_permute_batch_device(d_inputs: *const *const SvFe, d_tables: *const *const SvFe,
+                                                   count: usize, n: usize, form: c_int, flags: u32,
+                                                   d_permuted_inputs: *const *mut SvFe,
+                                                   d_permuted_tables: *const *mut SvFe,
+                                                   out_missing_rows: *mut u64, out_failed: *mut u64,
+                                                   device: c_int, stream: *mut c_void) -> c_int;
     pub fn sv_bn254_shplonk_work_elems(n_sets: usize, n: usize, elems: *mut u64) -> c_int;
     pub fn sv_bn254_shplonk_quotient_device(handle: u64, offset: usize, d_polys: *const *const SvFe,
                                             lens: *const u64, m: usize, sets: *const SvShplonkSet, n_sets: usize,
@@ -783,6 +796,36 @@ pub unsafe fn poly_eval_points_device(d_polys: &[*const Fr], lens: &[u64], point
                                                  points.as_ptr() as *const SvFe, points.len(), SV_MONTGOMERY, device,
                                                  stream, evals.as_mut_ptr() as *mut SvFe);
     (rc == SV_OK).then_some(evals)
+}
+
+/// halo2's permute_expression_pair for every lookup of a circuit in one call: lookup j's A' and S' go
+/// to `d_permuted_inputs[j]` and `d_permuted_tables[j]`.  Equal pointers in `d_tables` are one table,
+/// sorted once; `tables_sorted` promises that every table is already ascending and sorts none.
+/// `Err((status, rows))` holds the library's status and, for "not in table", per lookup the smallest
+/// row of A' whose value is not in its table (`u64::MAX` where the lookup is fine); `rows` is empty
+/// for every other refusal, whose words `sv_last_error` has.
+///
+/// # Safety
+/// Every pointer must point to `n` Montgomery elements on `device`, readable for `d_inputs` and
+/// `d_tables`, writable for the outputs, and no output may overlap anything else of the call.
+pub unsafe fn lookup_permute_batch_device(d_inputs: &[*const Fr], d_tables: &[*const Fr], n: usize, tables_sorted: bool,
+                                          d_permuted_inputs: &[*mut Fr], d_permuted_tables: &[*mut Fr], device: c_int,
+                                          stream: *mut c_void) -> Result<(), (c_int, Vec<u64>)> {
+    let count = d_inputs.len();
+    assert!(d_tables.len() == count && d_permuted_inputs.len() == count && d_permuted_tables.len() == count);
+    let mut rows = vec![u64::MAX; count];
+    let mut failed = u64::MAX;
+    let rc = sv_bn254_fr_lookup_permute_batch_device(d_inputs.as_ptr() as *const *const SvFe,
+                                                     d_tables.as_ptr() as *const *const SvFe, count, n, SV_MONTGOMERY,
+                                                     if tables_sorted { SV_LOOKUP_TABLES_SORTED } else { 0 },
+                                                     d_permuted_inputs.as_ptr() as *const *mut SvFe,
+                                                     d_permuted_tables.as_ptr() as *const *mut SvFe, rows.as_mut_ptr(),
+                                                     &mut failed, device, stream);
+    match (rc == SV_OK, failed != u64::MAX) {
+        (true, _) => Ok(()),
+        (false, true) => Err((rc, rows)),
+        (false, false) => Err((rc, Vec::new())),
+    }
 }
 
 impl Drop for ResidentBases {
